@@ -2,6 +2,14 @@
 """Headline benchmark: mel-frames/s and RTF of Tacotron2 + 60-iteration Griffin-Lim on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--L 100] [--iters 60]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  ``--dump-outputs DIR``
+also writes what the last timed step returned (``wav.npy``: every sentence's finished waveform, one
+after the other; ``frames.npy``: their frame counts) as float64 ``.npy`` files; the inputs and the
+seeds are fixed, so two builds can be compared output for output.  ``--full`` adds everything else
+to the line: per-stage and per-kernel times with the roofline, the CPU baseline, the configs[3]
+share and the Synthesizer.tts() regions (each with its own ``--no-*`` switch).
 
 A step = one pass of the synthesis hot path over one batch of synthetic sentences per rank:
 ids (already in HBM) -> encoder -> HIP decoder loop -> HIP postnet -> HIP Griffin-Lim (60 iters,
@@ -15,7 +23,8 @@ from the deterministic generator (seed 0), GL 60 iterations.  ``--model gst`` me
 instead: TacotronGST (config_tacotron_gst.json, 4 speakers, speaker b mod 4), B=32 sentences per
 GPU with L ~ U{60..160} (seed 4), style mel [B, 200, 80] ~ U[0,1) (seed 4), linear-spectrogram GL.
 
-Prints ONE JSON line on rank 0 (keys per the driver contract, plus roofline / cpu_baseline).
+Prints ONE JSON line on rank 0 (keys per the driver contract; with --full plus roofline /
+cpu_baseline and the other regions).
 """
 from __future__ import annotations
 
@@ -249,6 +258,25 @@ def collect_status(model):
     so a timed-out persistent loop can never hide inside a published measurement."""
     if hasattr(model, "synth_sync"):
         model.synth_sync()
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, frames, wav, hop):
+    """--dump-outputs: what the last timed step handed back on this rank, as float64 .npy files.
+    ``wav.npy`` holds every sentence's finished waveform (hop * (T - 1) samples, the part of its
+    row the step wrote) one after the other, ``frames.npy`` their frame counts T.  Above the budget
+    the waveform file keeps a fixed sample of positions (generator seed 0, ascending) instead."""
+    os.makedirs(path, exist_ok=True)
+    rows = [wav[k, :hop * (T - 1)] for k, T in enumerate(frames)]
+    flat = torch.cat(rows).to(torch.float64).cpu().numpy()
+    keep = (DUMP_BUDGET_BYTES - 8 * len(frames) - 4096) // 8
+    if flat.size > keep:
+        pick = np.random.Generator(np.random.PCG64(0)).choice(flat.size, size=keep, replace=False)
+        flat = flat[np.sort(pick)]
+    np.save(os.path.join(path, "frames.npy"), np.asarray(frames, dtype=np.float64))
+    np.save(os.path.join(path, "wav.npy"), flat)
 
 
 def _cpu_model():
@@ -497,7 +525,7 @@ def proxy_main(args, world, rank):
     ref = single_rank_reference(make_step(all_ids, mine, 1), args, world, rank, cpu, hop, 22050)
     tm = timed_region(make_step(all_ids, mine, world), args, world, cpu, hop, 22050)
     share = None
-    if world == 1 and args.model != "gst":
+    if world == 1 and args.model != "gst" and args.full:
         ids8, mine8 = configs3_share(args, 1000)
         share = share_record(timed_region(make_step(ids8, mine8, 1), args, 1, cpu, hop, 22050), len(mine8))
     if rank == 0:
@@ -586,10 +614,15 @@ def parse_args(argv=None):
     ap_.add_argument("--lengths", choices=["fixed", "uniform"], default=None,
                      help="fixed L (configs[1]) or L ~ U{60..160} (configs[2]/[3]); default by N")
     ap_.add_argument("--iters", type=int, default=60)
-    ap_.add_argument("--no-cpu-baseline", action="store_true")
-    ap_.add_argument("--no-profile", action="store_true")
+    ap_.add_argument("--dump-outputs", metavar="DIR", default=None,
+                     help="after the timed steps, write the last step's outputs (rank 0's share) as DIR/<name>.npy")
+    ap_.add_argument("--full", action="store_true",
+                     help="also measure everything beside the headline: stages, per-kernel profile and roofline, "
+                          "CPU baseline, configs[3] share and Synthesizer.tts() regions")
+    ap_.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap_.add_argument("--no-profile", action="store_true", help="--full without the per-kernel profile / roofline")
     ap_.add_argument("--no-share", action="store_true",
-                     help="N=1: skip the configs[3]-share region (configs3_share_1rank)")
+                     help="--full at N=1 without the configs[3]-share and Synthesizer.tts() regions")
     ap_.add_argument("--model", choices=["tacotron2", "gst"], default="tacotron2")
     ap_.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                      help="gloo + --proxy: CPU rehearsal of the launcher / partition / gather (no GPU)")
@@ -597,6 +630,13 @@ def parse_args(argv=None):
                      help="replace the GPU synthesis by a deterministic stand-in waveform per sentence "
                           "(launcher test only: the printed value is not a measurement)")
     args = ap_.parse_args(argv)
+    if args.proxy and args.dump_outputs:
+        ap_.error("--dump-outputs writes what the GPU path computed: not available with --proxy")
+    if not args.full:  # a plain run measures the headline only
+        if (args.no_cpu_baseline or args.no_profile or args.no_share) and os.environ.get("RANK", "0") == "0":
+            print("bench.py: --no-cpu-baseline / --no-profile / --no-share only trim a --full run; without --full "
+                  "none of those regions (nor the per-stage pass) runs", file=sys.stderr)
+        args.no_cpu_baseline = args.no_profile = args.no_share = True
     if args.batch is None:
         args.batch = 32 if args.model == "gst" else (64 if args.gpus > 1 else 1)
     if args.lengths is None:
@@ -630,8 +670,13 @@ def main():
                                 device, ap.hop_length, ap.sample_rate)
     if ref is not None:
         collect_status(model)
-    timing = timed_region(lambda seed: run_step(model, ap, all_ids, mine, world, seed=seed)[0], args, world, device,
-                          ap.hop_length, ap.sample_rate)
+    last = {}
+
+    def headline_step(seed):
+        last["frames"], last["wav"] = run_step(model, ap, all_ids, mine, world, seed=seed)
+        return last["frames"]
+
+    timing = timed_region(headline_step, args, world, device, ap.hop_length, ap.sample_rate)
     collect_status(model)
     elapsed, frames_per_step, ms_per_step, value, rtf = (timing[k] for k in ("elapsed", "frames_per_step",
                                                                            "ms_per_step", "value", "rtf"))
@@ -642,33 +687,38 @@ def main():
             dist.destroy_process_group()
         return
 
-    # ---- per-stage wall times (rank 0, one extra untimed step) and per-kernel profile
+    if args.dump_outputs and last:  # before any other region reuses the model's waveform buffer
+        dump_outputs(args.dump_outputs, last["frames"], last["wav"], ap.hop_length)
+
     gst = args.model == "gst"
-    if not gst:  # the timed loop ran tts_synth_run: warm the per-stage entry points (graphs, buffers) once
-        warm = model.inference_batch(ids)
-        ap.griffin_lim_batch(warm["mel_post"], warm["frames"], seed=7)
-    torch.cuda.synchronize()
-    s0 = time.perf_counter()
-    if gst:
-        style, spk = gst_inputs(len(all_ids), device)
-        sel = torch.as_tensor(mine, dtype=torch.long, device=device)
-        out = model.inference_batch(ids, speaker_ids=[spk[i] for i in mine], style_mel=style.index_select(0, sel))
-    else:
-        out = model.inference_batch(ids)
-    torch.cuda.synchronize()
-    s1 = time.perf_counter()
-    if gst:
-        ap.griffin_lim_batch(out["linear"], out["frames"], mode=audiomod._native.TTS_GL_FROM_LINEAR, seed=7)
-    else:
-        ap.griffin_lim_batch(out["mel_post"], out["frames"], seed=7)
-    torch.cuda.synchronize()
-    s2 = time.perf_counter()
-    dec_ms = model.last_timing.get("decoder_loop_ms", 0.0)
-    gl_ms = ap.last_gl_timing()["gl_loop_ms"]
-    stages = dict(tacotron2_ms=1000 * (s1 - s0), decoder_loop_ms=dec_ms, griffin_lim_ms=1000 * (s2 - s1),
-                  gl_iteration_loop_ms=gl_ms)
+    stages = None
     roofline = None
     kernels = {}
+    if args.full:
+        # ---- per-stage wall times (rank 0, one extra untimed step) and per-kernel profile
+        if not gst:  # the timed loop ran tts_synth_run: warm the per-stage entry points (graphs, buffers) once
+            warm = model.inference_batch(ids)
+            ap.griffin_lim_batch(warm["mel_post"], warm["frames"], seed=7)
+        torch.cuda.synchronize()
+        s0 = time.perf_counter()
+        if gst:
+            style, spk = gst_inputs(len(all_ids), device)
+            sel = torch.as_tensor(mine, dtype=torch.long, device=device)
+            out = model.inference_batch(ids, speaker_ids=[spk[i] for i in mine], style_mel=style.index_select(0, sel))
+        else:
+            out = model.inference_batch(ids)
+        torch.cuda.synchronize()
+        s1 = time.perf_counter()
+        if gst:
+            ap.griffin_lim_batch(out["linear"], out["frames"], mode=audiomod._native.TTS_GL_FROM_LINEAR, seed=7)
+        else:
+            ap.griffin_lim_batch(out["mel_post"], out["frames"], seed=7)
+        torch.cuda.synchronize()
+        s2 = time.perf_counter()
+        dec_ms = model.last_timing.get("decoder_loop_ms", 0.0)
+        gl_ms = ap.last_gl_timing()["gl_loop_ms"]
+        stages = dict(tacotron2_ms=1000 * (s1 - s0), decoder_loop_ms=dec_ms, griffin_lim_ms=1000 * (s2 - s1),
+                      gl_iteration_loop_ms=gl_ms)
     if not args.no_profile:
         B = len(ids)
         Lmean = float(np.mean([len(x) for x in ids]))
@@ -834,12 +884,10 @@ def main():
                    "parallelism": (f"sentence-sharded x{world} (LPT), RCCL gather-v of waveforms to rank 0"
                                    if world > 1 else "single GPU")},
         "rtf": rtf,
-        "roofline": roofline,
-        "cpu_baseline": cpu,
-        "stages_rank0": stages,
         "paths_rank0": paths,
-        "kernels_rank0": kernels,
     }
+    if args.full:
+        rec.update(roofline=roofline, cpu_baseline=cpu, stages_rank0=stages, kernels_rank0=kernels)
     rec.update(scaling_keys(timing, ref, world, share))
     if server is not None:
         rec["synthesizer_config_1rank"] = server

@@ -49,11 +49,11 @@ def test_launcher_spawns_n_ranks_with_configs3_default(n):
 
 
 def test_launcher_single_rank_default_is_configs1():
-    rec = _run("--gpus", "1", "--backend", "gloo", "--proxy", "--steps", "2", "--warmup", "0")
+    rec = _run("--gpus", "1", "--backend", "gloo", "--proxy", "--steps", "2", "--warmup", "0", "--full")
     assert rec["n_gpus"] == 1 and rec["world_size_seen"] == 1
     assert rec["config"]["sentences_per_gpu"] == 1 and rec["config"]["lengths"] == "fixed"
     assert rec["config"]["frames_per_step"] == 222  # L = 100 -> 2L + 22
-    # ... plus the N=8 line's per-rank workload on this one GPU: rank 0's share of configs[3]
+    # ... plus (--full) the N=8 line's per-rank workload on this one GPU: rank 0's share of configs[3]
     from conftest import load_pkg
     sh = load_pkg("sharding")
     lens = load_pkg("weights").synthetic_lengths(512, 3)
@@ -62,6 +62,16 @@ def test_launcher_single_rank_default_is_configs1():
     share = rec["configs3_share_1rank"]
     assert share["sentences"] == 64 and share["frames_per_step"] == sum(costs[i] for i in share0)
     assert "scaling_ref_1rank" not in rec and "efficiency" not in rec
+
+
+def test_plain_single_rank_line_is_the_headline_only():
+    """Without --full the N=1 line times its own steps and nothing else: --steps sets their number
+    and the configs[3]-share region stays out."""
+    rec = _run("--gpus", "1", "--backend", "gloo", "--proxy", "--steps", "3", "--warmup", "1")
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0
+    assert rec["config"]["frames_per_step"] == 222
+    assert abs(rec["value"] - 222 / (rec["ms_per_step"] * 1e-3)) < 1e-6 * rec["value"]
+    assert "configs3_share_1rank" not in rec
 
 
 def test_world_size_mismatch_is_refused():

@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU-box helper for the batch-1 (configs[1]) path: resident decoder / encoder tests, the event
-# trace, the bench line and its rocprofv3 kernel statistics (gpurun_out/b1_summary.txt).
+# trace, the bench line and its rocprofv3 kernel statistics ($BENCH_OUT/prof_b1_summary.txt, default bench_out/).
 set -o pipefail
 R=$(pwd)
 mkdir -p gpurun_out
@@ -12,7 +12,8 @@ import json;d=json.load(open('gpurun_out/trace.json'))
 print('trace us/step', round(d['us_per_step_trace'],3))
 for k,v in d['events_rel_step_start_us(min,median,max)'].items(): print(' ', k, v)
 print(d['last_cu'])"
-timeout -k 10 200 python bench.py --no-cpu-baseline --no-share > gpurun_out/bench_b1.json 2> gpurun_out/bench_b1.err && python tools/bench_digest.py gpurun_out/bench_b1.json || { tail -20 gpurun_out/bench_b1.err; exit 1; }
+O=$R/${BENCH_OUT:-bench_out} && mkdir -p $O
+timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-share > $O/bench_b1.json 2> $O/bench_b1.err && python tools/bench_digest.py $O/bench_b1.json || { tail -20 $O/bench_b1.err; exit 1; }
 cd /tmp && export TMPDIR=/tmp
-TTS_COOP=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_b1 -o run --output-format csv -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-profile --no-share > $R/gpurun_out/prof_b1_bench.json 2> $R/gpurun_out/prof_b1.err || { echo rocprof failed; tail -20 $R/gpurun_out/prof_b1.err; exit 1; }
-python $R/tools/rocprof_summary.py $R/gpurun_out/prof_b1/run_kernel_stats.csv $R/gpurun_out/prof_b1_summary.txt | head -14
+TTS_COOP=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_b1 -o run --output-format csv -- python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-profile --no-share > $O/prof_b1_bench.json 2> $O/prof_b1.err || { echo rocprof failed; tail -20 $O/prof_b1.err; exit 1; }
+python $R/tools/rocprof_summary.py $O/prof_b1/run_kernel_stats.csv $O/prof_b1_summary.txt | head -14

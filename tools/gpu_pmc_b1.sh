@@ -5,7 +5,7 @@
 set -o pipefail
 R=$(pwd)
 mkdir -p gpurun_out
-B="$R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-profile --no-share"
+B="$R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-profile --no-share"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/ks -o run --output-format csv -- python3 $B > $R/gpurun_out/ks.log 2>&1 || { echo "stats failed"; tail -5 $R/gpurun_out/ks.log; exit 1; }
 timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $R/gpurun_out/pf -o run --output-format csv -- python3 $B > $R/gpurun_out/pf.log 2>&1 || { echo "fetch pass failed"; tail -5 $R/gpurun_out/pf.log; exit 1; }
