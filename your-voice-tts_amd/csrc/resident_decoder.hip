@@ -79,6 +79,86 @@ __device__ __forceinline__ int res_candidate(int s, int nn, int np, int L) {
     return q < L ? q : -1;
 }
 
+// The eval mask's window of a step whose previous argmax is n (common_layers.py:207-213, Python's
+// negative-index wrap included): position cx = (n-2) mod L takes 0.01 max, positions [clo, chi] =
+// [n-1, min(n+2, L-1)] survive.  Everything here depends on (n, L) only, so a step knows it
+// before its query arrives; the code after the query consumes it with selects.  The step's result
+// is five weights: wcx at cx and ww[k] at clo + k, visited in position order as six slots
+// (cx before the window | entries 0-3 | cx after the window; an entry that is cx carries wcx).
+struct ResWin {
+    int cx, clo, chi;
+    bool in[4];    // entry k exists: clo + k <= chi
+    bool iscx[4];  // ... and is position cx (the mask's 0.01 max replaces it)
+    bool pre, post;  // cx lies before / after the window
+};
+__device__ __forceinline__ ResWin res_win(int n, int L) {
+    ResWin w;
+    w.cx = n >= 2 ? n - 2 : n - 2 + L;
+    w.clo = n >= 1 ? n - 1 : L - 1;
+    w.chi = min(n + 2, L - 1);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        w.in[k] = w.clo + k <= w.chi;
+        w.iscx[k] = w.in[k] && w.clo + k == w.cx;
+    }
+    w.pre = w.cx < w.clo;
+    w.post = w.cx > w.chi;
+    return w;
+}
+// The five weights from the window's unnormalised values c[k] (position clo + k) and the row
+// maximum rm: alpha[cx] = 0.01 rm, the rest of the row zero, then the normalisation (:213-216).
+__device__ __forceinline__ void res_weights(const ResWin& w, float rm, const float (&c)[4], float& wcx, float (&ww)[4]) {
+    float aw[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) aw[k] = (w.in[k] && !w.iscx[k]) ? c[k] : 0.f;
+    const float rs = ((aw[0] + aw[1]) + aw[2]) + aw[3];  // index order
+    const float vx = 0.01f * rm;
+    const float denom = rs + vx;
+    const float inv = 1.f / denom;
+    wcx = vx * inv;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ww[k] = aw[k] * inv;
+}
+// One channel of the context (bmm, :217): the slots' products summed in position order; an absent
+// slot leaves the partial sum as it is (no zero product is added).
+__device__ __forceinline__ float res_context(const ResWin& w, float wcx, const float (&ww)[4], float ex,
+                                             const float (&erow)[4]) {
+    const float px = wcx * ex;
+    float ctx = 0.f;
+    ctx = w.pre ? ctx + px : ctx;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float s = ctx + (w.iscx[k] ? px : ww[k] * erow[k]);
+        ctx = w.in[k] ? s : ctx;
+    }
+    ctx = w.post ? ctx + px : ctx;
+    return ctx;
+}
+// The weight at position p (0 outside the window)
+__device__ __forceinline__ float res_weight_at(const ResWin& w, float wcx, const float (&ww)[4], int p) {
+    const int d = p - w.clo;
+    const float v = d == 0 ? ww[0] : d == 1 ? ww[1] : d == 2 ? ww[2] : ww[3];
+    return p == w.cx ? wcx : ((p >= w.clo && p <= w.chi) ? v : 0.f);
+}
+// What the step leaves for later ones: the stop rule's tail alpha[L-2] + alpha[L-1]
+// (tacotron2.py:268) and the next step's n = argmax(prev_alpha) = 1 + the first argmax of
+// alpha[0..L-2] (0 when all zero), slots visited in position order.
+__device__ __forceinline__ int res_tail_next(const ResWin& w, float wcx, const float (&ww)[4], int L, float& tail) {
+    tail = res_weight_at(w, wcx, ww, L - 2) + res_weight_at(w, wcx, ww, L - 1);
+    float bv = 0.f;
+    int bi = -1;
+    auto consider = [&](bool present, int p, float wp) {
+        const bool take = present && p <= L - 2 && wp > bv;
+        bv = take ? wp : bv;
+        bi = take ? p : bi;
+    };
+    consider(w.pre, w.cx, wcx);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) consider(w.in[k], w.clo + k, w.iscx[k] ? wcx : ww[k]);
+    consider(w.post, w.cx, wcx);
+    return bi >= 0 ? bi + 1 : 0;
+}
+
 constexpr int SM_WDL = 16 * 16 * 32 * 4;  // floats of the decoder-LSTM LDS weight image (128 KiB)
 constexpr int SM_ST = 64;                  // biases, cell states, stop-rule state
 constexpr int SM_RQ = 4 * 64 * 4;          // query row [4 i4][64 lanes] float4 | attention CU scratch
@@ -254,12 +334,29 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
     const auto rpt = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.Pt), (short)0, ADIM * a.Lcap * 4, 0x00020000);
     auto prefetch_rows = [&](int nn) {
         // the rows the context can use after the mask: (nn-2) mod L and [nn-1, nn+2]
-        const int cx = (nn - 2 + L) % L, clo = nn >= 1 ? nn - 1 : L - 1, chi = min(nn + 2, L - 1);
+        const int cx = nn >= 2 ? nn - 2 : nn - 2 + L, clo = nn >= 1 ? nn - 1 : L - 1, chi = min(nn + 2, L - 1);
         ex = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(renc, (cx * ENC + tid) * 4, 0, VOLATILE_AUX));
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             erow[k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
                 renc, clo + k <= chi ? ((clo + k) * ENC + tid) * 4 : OOB_OFF, 0, VOLATILE_AUX));
+    };
+    // The rows for the step after one whose argmax was `from`: the window follows the argmax, which
+    // the forward attention moves by at most one position on most steps, so the registers already
+    // hold it (no load) or all but its last row (one load, the others shift down; a row past L-1
+    // reads 0 either way).  Four or five loads fewer ahead of the h_att poll (vmcnt is in order).
+    auto advance_rows = [&](int from, int nn) {
+        if (nn == from) return;
+        if (nn == from + 1 && from >= 1) {
+            ex = erow[0];
+            erow[0] = erow[1];
+            erow[1] = erow[2];
+            erow[2] = erow[3];
+            erow[3] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+                renc, nn + 2 <= L - 1 ? ((nn + 2) * ENC + tid) * 4 : OOB_OFF, 0, VOLATILE_AUX));
+        } else {
+            prefetch_rows(nn);
+        }
     };
     if (att_cu) {
         n = a.nidx[0];
@@ -473,11 +570,11 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         // 4) gather h_att_t (all waves); first wave 4 writes the mel row c of step t-1 (xh_dec, xctx
         //    still hold h_dec_{t-1}, ctx_{t-1}): off the critical path of step t-1's pre1 rows.  The
         //    attention CU first issues this step's attention operands (the encoder rows the mask can
-        //    keep, P at the candidate positions): in flight while h_att is awaited (a load issued
+        //    keep that it does not hold yet, P at the candidate positions): in flight while h_att is awaited (a load issued
         //    before the pre1 poll instead held that poll up by its latency, vmcnt being in order, and
         //    with it the XCD's prenet-2 rows: 1.2 us per step, round-4 trace)
         if (att_cu && t > 0) {
-            prefetch_rows(n);
+            advance_rows(n_prev, n);
             const int pos = res_candidate(tid >> 5, n, n_prev, L);
 #pragma unroll
             for (int m = 0; m < 4; ++m)
@@ -505,15 +602,14 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
             if (lane == 0) publish_xcd(Gq + (t & 1) * GR_TOTAL + 2 * qrow + qhalf, E + 3, s);
             if (tid == 0) { RES_EV(t, 8) }
         }
-        // 6) decoder LSTM over h_att_t (its h_dec_{t-1} half ran at the loop top); the attention
-        //    CU does this after its attention step, which is on the critical path (there it runs
-        //    while the other CUs' context gather waits out the XCD-local edge)
-        if (!att_cu) {
+        // 6) decoder LSTM over h_att_t (its h_dec_{t-1} half ran at the loop top).  The attention CU
+        //    too: the query rows are crossing the XCD meanwhile (when this half followed its context
+        //    publish instead, the CU idled here and was then the last to publish h_dec)
 #pragma unroll 2
-            for (int i = 0; i < 8; ++i) acc_d = dot4(wdl[(i * 16 + r) * 32 + ks], ld4(xh_att + i * 128 + ks * 4), acc_d);
-        }
+        for (int i = 0; i < 8; ++i) acc_d = dot4(wdl[(i * 16 + r) * 32 + ks], ld4(xh_att + i * 128 + ks * 4), acc_d);
         RES_MARK(5);
-        float wdef = 0.f;  // attention CU: this thread's weight of the step (stored after h_dec is published)
+        float wcx = 0.f, ww[4] = {0.f, 0.f, 0.f, 0.f};  // the step's five weights (ResWin)
+        int n_win = 0;  // attention CU: the n they belong to (alpha and the alignment row follow the h_dec publish)
         // 7) attention step.  After the forward mask the previous alpha is nonzero only on the
         //    previous window S' = W(n') = {(n'-2) mod L} + [n'-1, n'+2], so every position outside
         //    C = W(n) + S' + (S'+1) has mix = 1e-8 exactly and anj = 1e-8 * sigmoid <= 1e-8: the
@@ -694,9 +790,10 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         }
         if (att_cu) {
             const float* aold = abuf + (t & 1) * RES_LMAX;
-            float* anew = abuf + ((t & 1) ^ 1) * RES_LMAX;
             float* candv = scr + 2 * RES_WAVES;
-            const int cx = n >= 2 ? n - 2 : n - 2 + L, clo = n >= 1 ? n - 1 : L - 1, chi = min(n + 2, L - 1);
+            // the window of this step and the forward-attention mix of this thread's candidate: all
+            // of it known before the query arrives
+            const ResWin win = res_win(n, L);
             // candidate slot s = tid / 32 (32 lanes x 4 dims): its operands that do not depend on
             // the query are read before the query arrives
             const int sl = tid >> 5, sub = tid & 31;
@@ -705,6 +802,8 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
 #pragma unroll
             for (int m = 0; m < 4; ++m) xvd[m] = xv[sub + 32 * m];
             const float a_pos = pos >= 0 ? aold[pos] : 0.f, a_prev = pos > 0 ? aold[pos - 1] : 0.f;
+            const float mix = __fadd_rn(__fadd_rn(__fmul_rn(1.f - ufa, a_pos), __fmul_rn(ufa, a_prev)), 1e-8f);
+            RES_MARK(9);
             if (wave < 2) {  // query row pk = its two half-rows
                 for (int i = 0; i < a.sleep_q; ++i) __builtin_amdgcn_s_sleep(1);
                 float q0, q1;
@@ -717,30 +816,29 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
             if (flags[1]) break;
             RES_MARK(6);
             bool full = t == 0;
-            float rm = -INFINITY, cand = -INFINITY;
+            float rm = -INFINITY;
+            float cw[4] = {0.f, 0.f, 0.f, 0.f};  // the window's unnormalised weights an[clo + k]
             if (!full) {
                 float part = 0.f;
 #pragma unroll
                 for (int m = 0; m < 4; ++m) part += xvd[m] * tanh_fast(xq[sub + 32 * m] + ptc[m]);
                 const float e = sum32_dpp(part);
                 if (sub == 31) {
-                    float v = -INFINITY;
-                    if (pos >= 0) {
-                        const float sg = sigmoid_fast(e + vb);
-                        const float mix = __fadd_rn(__fadd_rn(__fmul_rn(1.f - ufa, a_pos), __fmul_rn(ufa, a_prev)), 1e-8f);
-                        v = __fmul_rn(mix, sg);
-                        an[pos] = v;
-                    }
+                    const float v = pos >= 0 ? __fmul_rn(mix, sigmoid_fast(e + vb)) : -INFINITY;
+                    if (pos >= 0) an[pos] = v;
                     candv[sl] = v;
                 }
                 __syncthreads();  // A2
                 if (tid == 0) { RES_EV(t, 10) }
                 RES_MARK(14);
-                // one LDS read per lane (slot lane % 16), the max by DPP, the window slots 1-4 by
-                // readlane below: no chain of dependent LDS reads
-                cand = candv[lane & 15];
+                // one LDS read per lane (slot lane % 16), the max by DPP, the window slots 1-4 (they
+                // hold exactly an[clo + k]: the same lane wrote both) by readlane: no chain of
+                // dependent LDS reads
+                const float cand = candv[lane & 15];
                 rm = wave_max_dpp(cand);
                 full = !(rm >= 1e-8f);  // uniform
+#pragma unroll
+                for (int k = 0; k < 4; ++k) cw[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cand), 1 + k));
             }
             if (full) {
                 // every position: wave w owns dims [16w, 16w + 16), lanes own positions
@@ -766,8 +864,8 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
                     for (int w = 0; w < RES_WAVES; ++w) e += red[w * RES_LMAX + j];
                     const float sg = sigmoid_fast(e + vb);
                     const float prev = j > 0 ? aold[j - 1] : 0.f;
-                    const float mix = __fadd_rn(__fadd_rn(__fmul_rn(1.f - ufa, aold[j]), __fmul_rn(ufa, prev)), 1e-8f);
-                    anj = __fmul_rn(mix, sg);
+                    const float mixj = __fadd_rn(__fadd_rn(__fmul_rn(1.f - ufa, aold[j]), __fmul_rn(ufa, prev)), 1e-8f);
+                    anj = __fmul_rn(mixj, sg);
                     an[j] = anj;
                 }
                 const float wmax = wave_max_dpp(anj);
@@ -776,73 +874,27 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
                 rm = -INFINITY;
 #pragma unroll
                 for (int k = 0; k < RES_WAVES; ++k) rm = fmaxf(rm, scr[2 * k + 1]);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) cw[k] = an[win.clo + k];
             }
             RES_MARK(7);
-            // the surviving window [n-1, n+2] without (n-2) mod L: its unnormalised weights once
-            // the surviving window's unnormalised weights: candidate slots 1-4 hold exactly an[clo + k]
-            // (the same lane wrote both); the full-L path reads them from an[]
-            float aw[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float c = full ? an[clo + k] : __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cand), 1 + k));
-                aw[k] = (clo + k <= chi && clo + k != cx) ? c : 0.f;
-            }
-            const float rs = ((aw[0] + aw[1]) + aw[2]) + aw[3];  // index order
-            const float vx = 0.01f * rm;  // alpha[n-2] = 0.01 * val
-            const float denom = rs + vx;
-            const float inv = 1.f / denom;
-            const float wcx = vx * inv;
-            float ww[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) ww[k] = aw[k] * inv;
-            auto weight = [&](int p) -> float {
-                if (p == cx) return wcx;
-                return (p >= clo && p <= chi) ? ww[p - clo] : 0.f;
-            };
-            const float tail = weight(L - 2) + weight(L - 1);  // tacotron2.py:268
-            float bv = 0.f;
-            int bi = -1;
-            auto consider = [&](int p) {
-                const float wp = weight(p);
-                if (p <= L - 2 && wp > bv) { bv = wp; bi = p; }
-            };
-            if (cx < clo) consider(cx);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (clo + k <= chi) consider(clo + k);
-            if (cx > chi) consider(cx);
-            float ctx = 0.f;
-            if (cx < clo) ctx += wcx * ex;
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (clo + k <= chi) ctx += (clo + k == cx ? wcx * ex : ww[k] * erow[k]);
-            if (cx > chi) ctx += wcx * ex;
+            // straight-line from here to the publish: the five weights, then this thread's channel
+            res_weights(win, rm, cw, wcx, ww);
+            const float ctx = res_context(win, wcx, ww, ex, erow);
             RES_MARK(15);
             publish_xcd(Gc + (t & 1) * GR_TOTAL + tid, E + 4, ctx);
-            if (tid == 0) publish_xcd(Gc + (t & 1) * GR_TOTAL + ENC, E + 4, tail);
             xctx[tid] = ctx;  // this CU skips the gather
-            if (tid == 0) xctx[ENC] = tail;
             if (tid == 0) { RES_EV(t, 11) }
+            // off the chain of the 512 channels: the tail (the stop CU's wave 4 waits for it beside
+            // the context) and, after it, the next step's n
+            float tail;
+            const int n_next = res_tail_next(win, wcx, ww, L, tail);
+            if (tid == 0) publish_xcd(Gc + (t & 1) * GR_TOTAL + ENC, E + 4, tail);
+            if (tid == 0) xctx[ENC] = tail;
             RES_MARK(8);
-            // off the critical path: this step's alpha (next step's prev_alpha) and alignment row
-            wdef = tid < L ? weight(tid) : 0.f;
+            n_win = n;
             n_prev = n;
-            n = bi >= 0 ? bi + 1 : 0;  // argmax(prev_alpha) of the next step (its loads: h_att wait)
-            // the deferred decoder-LSTM h_att half is on this CU's h_dec path: four chunks' LDS
-            // operands in flight at a time (the two-chunk loop waited out eight LDS round trips)
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                float4 wv[4], xv4[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    wv[j] = wdl[((4 * h + j) * 16 + r) * 32 + ks];
-                    xv4[j] = ld4(xh_att + (4 * h + j) * 128 + ks * 4);
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc_d = dot4(wv[j], xv4[j], acc_d);
-                asm volatile("" ::: "memory");
-            }
-            RES_MARK(9);
+            n = n_next;  // argmax(prev_alpha) of the next step (its loads: h_att wait)
         }
         // this wave's prenet-1 row weights (step 11) from the XCD's L2, in flight while the context
         // (and then h_dec) is awaited
@@ -905,6 +957,7 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         // publish: the eight attention CUs are the h_dec edge's last publishers
         if (att_cu) {
             float* anew = abuf + ((t & 1) ^ 1) * RES_LMAX;
+            const float wdef = tid < L ? res_weight_at(res_win(n_win, L), wcx, ww, tid) : 0.f;
             if (tid < L) anew[tid] = wdef;
             if (att_log && t < a.hist_cap && tid < a.Lalign) a.align_hist[(int64_t)t * a.Lalign + tid] = wdef;
         }

@@ -438,7 +438,7 @@ class Tacotron2:
                     resident_kind=int(res.value), encoder_resident=bool(enc.value), encoder_path=int(enc.value))
 
     RESIDENT_PHASES = ("att_early_wait_pre1", "prenet2_row", "wait_prenet2", "att_lstm_prenet", "att_cell_gather",
-                       "query_dec_early", "wait_query", "energies_max", "weights_ctx_publish", "next_prefetch",
+                       "query_dec_early", "wait_query", "energies_max", "weights_ctx_publish", "dec_lstm_hatt",
                        "wait_ctx", "dec_lstm_ctx", "dec_cell_gather", "fused_rows", "cand_energies", "weights_ctx")
 
     def profile_resident_phases(self):
