@@ -110,8 +110,9 @@ void tts_decoder_destroy(tts_decoder* d);
  *   align    [dev]  fp32 [B][steps_cap][Lmax]  attention weights per step (may be NULL)
  *   n_steps  [host] int32 [B] out: decoder steps taken by each sentence
  * steps_cap must be >= max_steps + 20 (the reference can run up to 20 steps past the cap once
- * every stop flag is set, layers/tacotron2.py:271-277).  Entries past n_steps[b] are left
- * untouched.  Synchronises `stream` once per chunk of steps to read the stop flags. */
+ * every stop flag is set, layers/tacotron2.py:271-277).  Entries past n_steps[b] are zero up
+ * to the batch's longest run and left untouched beyond it.  Synchronises `stream` once per
+ * chunk of steps to read the stop flags. */
 tts_status tts_decoder_run(tts_decoder* d, const float* enc, const int32_t* lens, int B, int Lmax,
                            int max_steps, int steps_cap, float* mel, float* stop, float* align,
                            int32_t* n_steps, void* stream);

@@ -10,6 +10,7 @@ image and not on the numeric path) stubbed in ``sys.modules``; it is built with
 ``utils.generic_utils.setup_model`` from ``config_tacotron2.json`` plus per-case flag
 overrides, loaded with weights from ``weights.py``'s deterministic generator, put in eval
 mode and run through ``inference`` on seeded ids.  Inputs and outputs are saved.
+``pool_fwdmask.npz`` (target "pool") holds ten such runs, L = 2..40, in one file.
 
 Tacotron / TacotronGST half (gst_*.npz, taco_*.npz): the reference ``Tacotron`` /
 ``TacotronGST`` (``models/tacotron.py``, ``models/tacotrongst.py``) built the same way from
@@ -136,6 +137,46 @@ def make_model_fixtures(cases=CASES):
             mel_post=mel_post[0].numpy(), align=align[0].numpy(), stop=stop[0, :, 0].numpy(),
             flags=np.array(repr(flags)))
         print(f"{name}: L={L} T={mel.shape[1]} flags={flags}")
+
+
+# A pool of short sentences for the every-sentence batch tests (tests/test_gpu_multilaunch_batch.py):
+# synthesize.py's configuration (forward attention + eval mask, default cap), one reference run at
+# batch 1 per length, all in ONE file whose name does not start with t2_ (test_gpu_parity.py globs
+# t2_*.npz into single-sentence cases).  Lengths sit below, on and above the 16-position edges of the
+# attention kernels and go down to L = 2, the shortest the reference's forward mask can index.
+POOL_LENGTHS = (2, 3, 5, 8, 13, 16, 17, 24, 31, 40)
+
+
+def make_pool_fixture():
+    import torch
+    _stub_text_deps()
+    sys.path.insert(0, REF)
+    from utils.generic_utils import load_config, setup_model
+    torch.set_num_threads(os.cpu_count())
+    C = load_config(os.path.join(REF, "config_tacotron2.json"))
+    C.num_speakers = 0
+    C.update(dict(forward_attn_mask=True))
+    model = setup_model(130, 0, C)
+    sd = weights.tacotron2_weights(0, num_chars=130, location_attn=C.location_attn, trans_agent=C.transition_agent)
+    assert list(model.state_dict().keys()) == list(sd.keys())
+    model.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
+    model.eval()
+    flags = dict(attn_norm=C.attention_norm, forward_attn=C.use_forward_attn,
+                 trans_agent=C.transition_agent, forward_attn_mask=C.forward_attn_mask,
+                 location_attn=C.location_attn, attn_win=C.windowing,
+                 max_decoder_steps=model.decoder.max_decoder_steps)
+    out = dict(flags=np.array(repr(flags)), lengths=np.array(POOL_LENGTHS, dtype=np.int64))
+    for L in POOL_LENGTHS:
+        ids = weights.synthetic_ids(L, 700 + L)
+        with torch.no_grad():
+            x = torch.from_numpy(ids).unsqueeze(0)
+            enc = model.encoder.inference(model.embedding(x).transpose(1, 2))
+            mel, mel_post, align, stop = model.inference(x)
+        out.update({f"ids_L{L}": ids, f"enc_L{L}": enc[0].numpy(), f"mel_L{L}": mel[0].numpy(),
+                    f"mel_post_L{L}": mel_post[0].numpy(), f"align_L{L}": align[0].numpy(),
+                    f"stop_L{L}": stop[0, :, 0].numpy()})
+        print(f"pool_fwdmask: L={L} T={mel.shape[1]}")
+    np.savez_compressed(os.path.join(HERE, "pool_fwdmask.npz"), **out)
 
 
 SPEAKER_CASES = [
@@ -511,7 +552,9 @@ def make_audio_test_fixture():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["model", "speakers", "prenet_bn", "taco", "taco_bn", "truncated", "teacher", "text", "split", "gl"]
+    which = sys.argv[1:] or ["model", "speakers", "prenet_bn", "taco", "taco_bn", "truncated", "teacher", "text", "split", "gl", "pool"]
+    if "pool" in which:
+        make_pool_fixture()
     if "taco_bn" in which:
         make_taco_fixtures(TACO_BN_CASES)
     if "prenet_bn" in which:

@@ -100,7 +100,8 @@ def test_encoder_ragged_batch():
 
 
 def test_batched_ragged_decoder_matches_batch1():
-    """A padded batch: every sentence gets exactly its batch-1 reference result."""
+    """A padded batch: every sentence gets exactly its batch-1 reference result.  Five sentences go
+    to the resident batch decoder as launches of 4 + 1."""
     cases = ["t2_fwdmask_L40", "t2_fwdmask_L12", "t2_fwdmask_L100", "t2_fwdmask_L12", "t2_fwdmask_L40"]
     zs = [golden(c) for c in cases]
     m = _model(golden_flags(zs[0]))
@@ -109,6 +110,7 @@ def test_batched_ragged_decoder_matches_batch1():
     for b, z in enumerate(zs):
         enc[b, :len(z["ids"])] = torch.from_numpy(z["enc"])
     out = m.inference_batch(None, enc=enc.cuda(), lens=[len(z["ids"]) for z in zs])
+    assert m.last_timing["resident_kind"] == 2, "the resident batch decoder did not serve this batch"
     for b, z in enumerate(zs):
         _check_decoder(out, b, z)
 

@@ -80,6 +80,12 @@ def _fix(name):
     # two launches of 4 (groups), ragged
     ["t2_fwdmask_L12", "t2_fwdmask_L40", "t2_fwdmask_L100", "t2_fwdmask_L12",
      "t2_fwdmask_L100", "t2_fwdmask_L40", "t2_fwdmask_L12", "t2_fwdmask_L100"],
+    # 4 + 1: the last launch holds one sentence (the NB = 2 kernel beside a padding sentence of
+    # L = 0), one that none of the four before it equals
+    ["t2_fwdmask_L12", "t2_fwdmask_L100", "t2_fwdmask_L100", "t2_fwdmask_L12", "t2_fwdmask_L40"],
+    # 4 + 3
+    ["t2_fwdmask_L100", "t2_fwdmask_L12", "t2_fwdmask_L40", "t2_fwdmask_L100",
+     "t2_fwdmask_L40", "t2_fwdmask_L100", "t2_fwdmask_L12"],
 ])
 def test_resident_batch_synthesis_configuration_vs_reference(cases):
     """synthesize.py's configuration (forward attention + eval mask, sigmoid) in ragged batches."""

@@ -16,11 +16,9 @@ T2_CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDE
 T2_CASES = [c for c in T2_CASES if not c.endswith("_cap3000") or os.environ.get("TTS_SLOW_ORACLE") == "1"]
 
 
-@pytest.mark.parametrize("case", T2_CASES)
-@pytest.mark.parametrize("dtype", [np.float32, np.float64])
-def test_tacotron2_oracle_matches_reference(case, dtype):
-    z = golden(case)
-    fl = golden_flags(z)
+def _check_t2_oracle(z, dtype):
+    """Tacotron2Oracle against one reference run z (ids, enc, mel, mel_post, align, stop) at flags fl."""
+    fl = z["flags"]
     sd = weights_mod().tacotron2_weights(0, location_attn=fl["location_attn"], trans_agent=fl["trans_agent"])
     o = Tacotron2Oracle(sd, dtype=dtype, **fl)
     enc = o.encoder(z["ids"])
@@ -35,6 +33,31 @@ def test_tacotron2_oracle_matches_reference(case, dtype):
     assert np.abs(align - z["align"]).max() < 1e-5
     assert np.abs(stop - z["stop"]).max() < 1e-5
     assert rel_rms(o.postnet(z["mel"]), z["mel_post"]) < 1e-5
+
+
+@pytest.mark.parametrize("case", T2_CASES)
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_tacotron2_oracle_matches_reference(case, dtype):
+    z = golden(case)
+    _check_t2_oracle(dict({k: z[k] for k in ("ids", "enc", "mel", "mel_post", "align", "stop")},
+                          flags=golden_flags(z)), dtype)
+
+
+POOL_LENGTHS = [int(L) for L in golden("pool_fwdmask")["lengths"]]
+
+
+@pytest.mark.parametrize("L", POOL_LENGTHS)
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_tacotron2_oracle_matches_reference_pool(L, dtype):
+    """The short-sentence pool (tests/golden/pool_fwdmask.npz, L = 2..40, synthesize.py's
+    configuration): every sentence held to the reference run like the t2_* fixtures, at the same
+    tolerances.  The first reference pinning of the oracle below L = 12, where the forward mask's
+    negative-index wrap and the clipped window overlap."""
+    z = golden("pool_fwdmask")
+    assert POOL_LENGTHS == [2, 3, 5, 8, 13, 16, 17, 24, 31, 40]
+    s = {k: z[f"{k}_L{L}"] for k in ("ids", "enc", "mel", "mel_post", "align", "stop")}
+    assert len(s["ids"]) == L and s["mel"].shape[0] == 2 * L + 22
+    _check_t2_oracle(dict(s, flags=golden_flags(z)), dtype)
 
 
 def test_stop_rule_frame_count_2L_plus_22():

@@ -610,10 +610,14 @@ tts_status tts_decoder_create(const tts_decoder_config* cfg, const tts_tensor* t
     if (Bc > 16) {
         d->ntf = (Bc + 15) / 16;
         const size_t rows = (size_t)d->ntf * 16;
-        CK(dmalloc(d, &d->xaf, 2 * rows * XA));
-        CK(dmalloc(d, &d->hattf, 2 * rows * HATT));
-        CK(dmalloc(d, &d->hdecf, 2 * rows * HDEC));
-        CK(dmalloc(d, &d->pre1f, rows * PRE));
+        // three m-tiles run the four-tile kernel (sgemm.hip: launch_role): at ntf == 3 its fourth
+        // tile of chunk c is tile 0 of chunk c + 1, one tile (256 floats) past the mirror at the
+        // last chunk.  The rows of that tile are never stored; the slack keeps the read in bounds.
+        const size_t slack = d->ntf == 3 ? 256 : 0;
+        CK(dmalloc(d, &d->xaf, 2 * rows * XA + slack));
+        CK(dmalloc(d, &d->hattf, 2 * rows * HATT + slack));
+        CK(dmalloc(d, &d->hdecf, 2 * rows * HDEC + slack));
+        CK(dmalloc(d, &d->pre1f, rows * PRE + slack));
     }
     CK(dmalloc(d, &d->epart, (size_t)Bc * QE_TILES * Lc));
     if (cfg->location_attn) CK(dmalloc(d, &d->locf, (size_t)Bc * NLOC * Lc));
@@ -1166,6 +1170,12 @@ tts_status decoder_run(tts_decoder* d, const float* enc, const int32_t* lens, in
                                  (size_t)nmax * Lmax * 4, B, hipMemcpyDeviceToDevice, s));
     // the mel history is written unguarded by done[] (see EPI_MEL_FUSED): zero rows past n_steps
     TTS_HIP(launch_zero_tail(mel, (int64_t)steps_cap * nm, d->n_steps, (int)nm, nmax, B, s));
+    // stop and alignment rows are written under done[]: past n_steps the histories still hold the
+    // rows of an earlier, longer run in this slot (batch 1 has no such rows: nmax = n_steps[0])
+    if (B > 1) {
+        TTS_HIP(launch_zero_tail(stop, steps_cap, d->n_steps, 1, nmax, B, s));
+        if (align) TTS_HIP(launch_zero_tail(align, (int64_t)steps_cap * Lmax, d->n_steps, Lmax, nmax, B, s));
+    }
     }
     if (s != cs) {
         TTS_HIP(hipEventRecord(d->ev_out, s));
