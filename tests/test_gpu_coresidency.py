@@ -159,6 +159,42 @@ def test_resident_decoder_timeout_reruns_multilaunch():
     assert m2.last_timing["resident"] and again["frames"] == want["frames"] == [z["mel"].shape[0]]
 
 
+def test_batched_resident_decoder_not_launched_reruns_multilaunch():
+    """A batch of 3 short sentences under TTS_CU_CAP: the host occupancy check refuses the batched
+    resident decoder's launch, nothing runs on the device, and the batch starts again on the
+    multi-launch path, bitwise that path's output.  The handle gives the batched form up for its
+    life: the same batch without the cap is multi-launch again, with the same bits."""
+    w = load_pkg("weights")
+    sents = [w.synthetic_ids(2, 301), golden("t2_fwdmask_L12")["ids"], w.synthetic_ids(7, 302)]
+    lens = [len(x) for x in sents]
+    ids = torch.zeros(3, max(lens), dtype=torch.long)
+    for b, x in enumerate(sents):
+        ids[b, :lens[b]] = torch.from_numpy(np.asarray(x))
+    m = _t2()
+    enc = m.encode(ids.cuda(), lens)  # one encoder output for all
+    ref = m.inference_batch(None, enc=enc, lens=lens)
+    assert m.last_timing["resident_kind"] == 2
+    with _env(TTS_RESIDENT_BATCH=0):
+        ml = _t2()
+        want = ml.inference_batch(None, enc=enc, lens=lens)
+        assert ml.last_timing["resident_kind"] == 0
+    assert want["frames"] == ref["frames"]
+
+    def same(got):
+        for k in ("mel", "mel_post", "align", "stop"):
+            assert torch.equal(got[k], want[k]), k
+        assert got["frames"] == want["frames"]
+
+    fb = _t2()
+    with _env(TTS_CU_CAP=8):
+        got = fb.inference_batch(None, enc=enc, lens=lens)
+        assert fb.last_timing["resident_kind"] == 0
+        same(got)
+    again = fb.inference_batch(None, enc=enc, lens=lens)
+    assert fb.last_timing["resident_kind"] == 0
+    same(again)
+
+
 def test_batched_resident_encoder_matches_per_step_launches():
     """The batched resident BiLSTM (encoder_resident_batch_kernel: XCD-local hand-offs, MFMA gate
     rows) on a ragged 64-sentence batch against the per-step launches it replaces (TTS_CU_CAP makes

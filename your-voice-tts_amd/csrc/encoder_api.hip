@@ -9,13 +9,10 @@
 #include <algorithm>
 #include <map>
 #include <string>
-#include <unordered_map>
-#include <vector>
-
-#include <cstdlib>
 
 #include "conv1d.h"
 #include "encoder_resident.h"
+#include "host_util.h"
 #include "resident.h"
 #include "sgemm.h"
 
@@ -31,7 +28,7 @@ struct tts_encoder {
     int num_chars = 0, Bcap = 0, Lcap = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
-    std::vector<void*> allocs;
+    DeviceAllocs dev;
     float* emb = nullptr;
     float* spk = nullptr;  // speaker_embedding.weight [nspk][512] (models/tacotron2.py:32-34), or null
     int nspk = 0;
@@ -71,15 +68,6 @@ struct tts_encoder {
 };
 
 namespace {
-
-template <typename T>
-tts_status emalloc(tts_encoder* e, T** p, size_t n) {
-    void* q = nullptr;
-    TTS_HIP(hipMalloc(&q, n * sizeof(T) + 16));
-    e->allocs.push_back(q);
-    *p = static_cast<T*>(q);
-    return TTS_OK;
-}
 
 tts_status enqueue_encoder(tts_encoder* e, int B, int Lmax, int frames, hipStream_t s, bool resident = false) {
     // outputs past L_b are zero (the batch-1 resident form runs one sentence of length Lmax: it
@@ -168,10 +156,8 @@ tts_status enqueue_encoder_resident(tts_encoder* e, int Lmax, bool zero_state, h
     e->rgran_clear = true;
     EncResArgs a{};
     a.w = e->rw;
-    static const int enc_first_sleep = [] {
-        const char* v = getenv("TTS_ENC_FIRST_SLEEP");
-        return v ? atoi(v) : 2;  // round 6: ~-9 us per configs[1] sentence (tools/cases_sleep.txt)
-    }();
+    // default 2, round 6: ~-9 us per configs[1] sentence (tools/cases_sleep.txt)
+    static const int enc_first_sleep = env_int("TTS_ENC_FIRST_SLEEP", 2);
     a.first_sleep = enc_first_sleep;
     a.xi = e->xi;
     a.L = Lmax;
@@ -200,7 +186,7 @@ void tts_encoder_destroy(tts_encoder* e) {
     for (auto& kv : e->rgraphs) (void)hipGraphExecDestroy(kv.second);
     for (auto& kv : e->bgraphs) (void)hipGraphExecDestroy(kv.second);
     if (e->host_status) (void)hipHostFree(e->host_status);
-    for (void* p : e->allocs) (void)hipFree(p);
+    e->dev.free_all();
     for (hipEvent_t ev : {e->ev_in, e->ev_out})
         if (ev) (void)hipEventDestroy(ev);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -212,14 +198,9 @@ tts_status tts_encoder_create(const tts_tensor* tensors, int n_tensors, int max_
     TTS_CHECK(tensors && out, TTS_ERR_INVALID, "null argument");
     TTS_CHECK(max_batch >= 1 && max_batch <= 64, TTS_ERR_UNSUPPORTED, "max_batch must be in [1, 64]");
     TTS_CHECK(max_len >= 1 && max_len <= 4096, TTS_ERR_UNSUPPORTED, "max_len must be in [1, 4096]");
-    std::unordered_map<std::string, std::pair<const float*, int64_t>> wm;
-    for (int i = 0; i < n_tensors; ++i) wm[tensors[i].key] = {tensors[i].data, tensors[i].numel};
-    auto get = [&](const std::string& k, int64_t numel) -> const float* {
-        auto it = wm.find(k);
-        if (it == wm.end()) { set_error("missing weight " + k); return nullptr; }
-        if (numel >= 0 && it->second.second != numel) { set_error("weight " + k + " has wrong size"); return nullptr; }
-        return it->second.first;
-    };
+    const WeightMap weights(tensors, n_tensors);
+    const auto& wm = weights.m;
+    auto get = [&](const std::string& k, int64_t numel) { return weights.get(k, numel); };
     auto* e = new tts_encoder();
     hipStream_t s = static_cast<hipStream_t>(stream);
     auto fail = [&](tts_status code) { tts_encoder_destroy(e); return code; };
@@ -240,7 +221,7 @@ tts_status tts_encoder_create(const tts_tensor* tensors, int n_tensors, int max_
     auto it = wm.find("embedding.weight");
     if (it == wm.end() || it->second.second % EDIM) { set_error("missing/bad embedding.weight"); return fail(TTS_ERR_INVALID); }
     e->num_chars = (int)(it->second.second / EDIM);
-    CK(emalloc(e, &e->emb, (size_t)e->num_chars * EDIM));
+    CK(e->dev.alloc(&e->emb, (size_t)e->num_chars * EDIM));
     HK(hipMemcpyAsync(e->emb, it->second.first, sizeof(float) * e->num_chars * EDIM, hipMemcpyDeviceToDevice, s));
     if (auto sp = wm.find("speaker_embedding.weight"); sp != wm.end()) {
         if (sp->second.second % EDIM || sp->second.second == 0) {
@@ -248,7 +229,7 @@ tts_status tts_encoder_create(const tts_tensor* tensors, int n_tensors, int max_
             return fail(TTS_ERR_INVALID);
         }
         e->nspk = (int)(sp->second.second / EDIM);
-        CK(emalloc(e, &e->spk, (size_t)e->nspk * EDIM));
+        CK(e->dev.alloc(&e->spk, (size_t)e->nspk * EDIM));
         HK(hipMemcpyAsync(e->spk, sp->second.first, sizeof(float) * e->nspk * EDIM, hipMemcpyDeviceToDevice, s));
     }
     for (int l = 0; l < 3; ++l) {
@@ -260,22 +241,22 @@ tts_status tts_encoder_create(const tts_tensor* tensors, int n_tensors, int max_
         const float* mu = get(pre + "1.running_mean", EDIM);
         const float* var = get(pre + "1.running_var", EDIM);
         if (!w || !bias || !g || !be || !mu || !var) return fail(TTS_ERR_INVALID);
-        CK(emalloc(e, &e->Wc[l], (size_t)EDIM * 5 * EDIM));
-        CK(emalloc(e, &e->sc[l], EDIM));
-        CK(emalloc(e, &e->sh[l], EDIM));
+        CK(e->dev.alloc(&e->Wc[l], (size_t)EDIM * 5 * EDIM));
+        CK(e->dev.alloc(&e->sc[l], EDIM));
+        CK(e->dev.alloc(&e->sh[l], EDIM));
         HK(conv_pack(w, EDIM, EDIM, 5, e->Wc[l], s));
-        CK(emalloc(e, &e->Wcf[l], (size_t)EDIM * 5 * EDIM));
+        CK(e->dev.alloc(&e->Wcf[l], (size_t)EDIM * 5 * EDIM));
         HK(conv_frag_tap_ok(EDIM) ? conv_pack_frag_tap(e->Wc[l], EDIM, 5, EDIM, e->Wcf[l], s)
                                   : conv_pack_frag(e->Wc[l], EDIM * 5, EDIM, e->Wcf[l], s));
         if (conv_frag_tap_ok(EDIM)) {
-            CK(emalloc(e, &e->Wcf16[l], (size_t)EDIM * 5 * EDIM));
+            CK(e->dev.alloc(&e->Wcf16[l], (size_t)EDIM * 5 * EDIM));
             HK(conv_pack_frag_tap16(e->Wc[l], EDIM, 5, EDIM, e->Wcf16[l], s));
         }
         HK(fold_bn(bias, g, be, mu, var, EDIM, 1e-5f, e->sc[l], e->sh[l], s));
     }
-    CK(emalloc(e, &e->Wp, (size_t)EDIM * 2 * EG));
-    CK(emalloc(e, &e->bp, 2 * EG));
-    CK(emalloc(e, &e->Whh, sgemm_packed_floats(EG, EH) * 2));
+    CK(e->dev.alloc(&e->Wp, (size_t)EDIM * 2 * EG));
+    CK(e->dev.alloc(&e->bp, 2 * EG));
+    CK(e->dev.alloc(&e->Whh, sgemm_packed_floats(EG, EH) * 2));
     const char* sfx[2] = {"", "_reverse"};
     for (int d = 0; d < 2; ++d) {
         const std::string pre = "encoder.lstm.";
@@ -289,42 +270,41 @@ tts_status tts_encoder_create(const tts_tensor* tensors, int n_tensors, int max_
         HK(sgemm_pack_bias(bih, bhh, EG, ROWMAP_IDENTITY, 0, e->bp + d * EG, s));
         HK(sgemm_pack(whh, EH, nullptr, 0, EG, ROWMAP_LSTM, EH, e->Whh + d * sgemm_packed_floats(EG, EH), s));
     }
-    CK(emalloc(e, &e->Wpf, (size_t)EDIM * 2 * EG));
+    CK(e->dev.alloc(&e->Wpf, (size_t)EDIM * 2 * EG));
     HK(conv_frag_tap_ok(EDIM) ? conv_pack_frag_tap(e->Wp, EDIM, 1, 2 * EG, e->Wpf, s)
                               : conv_pack_frag(e->Wp, EDIM, 2 * EG, e->Wpf, s));
     e->Bcap = max_batch;
     e->Lcap = max_len;
     const size_t BL = (size_t)max_batch * max_len;
-    CK(emalloc(e, &e->ids, BL));
-    CK(emalloc(e, &e->T, max_batch));
-    CK(emalloc(e, &e->act0, BL * EDIM));
-    CK(emalloc(e, &e->act1, BL * EDIM));
-    CK(emalloc(e, &e->xi, BL * 2 * EG));
-    CK(emalloc(e, &e->h, (size_t)4 * max_batch * EH));
-    CK(emalloc(e, &e->c, (size_t)2 * max_batch * EH));
-    CK(emalloc(e, &e->out, BL * EDIM));
-    CK(emalloc(e, &e->part, CONV_SPLITK_FLOATS + CONV_TICKETS));  // partials, then ticket words (zero at rest)
+    CK(e->dev.alloc(&e->ids, BL));
+    CK(e->dev.alloc(&e->T, max_batch));
+    CK(e->dev.alloc(&e->act0, BL * EDIM));
+    CK(e->dev.alloc(&e->act1, BL * EDIM));
+    CK(e->dev.alloc(&e->xi, BL * 2 * EG));
+    CK(e->dev.alloc(&e->h, (size_t)4 * max_batch * EH));
+    CK(e->dev.alloc(&e->c, (size_t)2 * max_batch * EH));
+    CK(e->dev.alloc(&e->out, BL * EDIM));
+    CK(e->dev.alloc(&e->part, CONV_SPLITK_FLOATS + CONV_TICKETS));  // partials, then ticket words (zero at rest)
     HK(hipMemsetAsync(e->part + CONV_SPLITK_FLOATS, 0, CONV_TICKETS * sizeof(int), s));
     {
-        const char* env = getenv("TTS_RESIDENT");
         int dev = 0, ncu = 0, rate_khz = 0;
-        if (!(env && env[0] == '0') && hipGetDevice(&dev) == hipSuccess &&
+        if (!env_is("TTS_RESIDENT", '0') && hipGetDevice(&dev) == hipSuccess &&
             hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu >= 128 &&
             hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, dev) == hipSuccess && rate_khz > 0) {
             float* w4 = nullptr;
-            CK(emalloc(e, &w4, encoder_resident_weight_float4() * 4));
+            CK(e->dev.alloc(&w4, encoder_resident_weight_float4() * 4));
             e->rw = reinterpret_cast<float4*>(w4);
-            CK(emalloc(e, &e->rgran, encoder_resident_granules()));
+            CK(e->dev.alloc(&e->rgran, encoder_resident_granules()));
             HK(encoder_resident_pack(get("encoder.lstm.weight_hh_l0", (int64_t)EG * EH),
                                      get("encoder.lstm.weight_hh_l0_reverse", (int64_t)EG * EH), e->rw, s));
             HK(hipHostMalloc(reinterpret_cast<void**>(&e->host_status), sizeof(int)));
             if (max_batch >= 2) {
-                CK(emalloc(e, &e->whh_raw, (size_t)2 * EG * EH));
+                CK(e->dev.alloc(&e->whh_raw, (size_t)2 * EG * EH));
                 HK(hipMemcpyAsync(e->whh_raw, get("encoder.lstm.weight_hh_l0", (int64_t)EG * EH), sizeof(float) * EG * EH,
                                   hipMemcpyDeviceToDevice, s));
                 HK(hipMemcpyAsync(e->whh_raw + (size_t)EG * EH, get("encoder.lstm.weight_hh_l0_reverse", (int64_t)EG * EH),
                                   sizeof(float) * EG * EH, hipMemcpyDeviceToDevice, s));
-                CK(emalloc(e, &e->bgran, encoder_resident_batch_granules()));
+                CK(e->dev.alloc(&e->bgran, encoder_resident_batch_granules()));
             }
             e->rtmo = (long long)rate_khz * 50;  // 50 ms per hand-off wait
             e->resident = true;
@@ -379,10 +359,7 @@ tts_status tts_encoder_run_state(tts_encoder* e, const int32_t* ids, const int32
     }
     // the batch-1 convs are enqueued directly: a graph launch followed by the resident launch left
     // the GPU idle ~8.7 us between them (configs[1] timeline, round 5); TTS_ENC_GRAPH=1 restores it
-    static const bool conv_graph = [] {
-        const char* v = getenv("TTS_ENC_GRAPH");
-        return v && v[0] == '1';
-    }();
+    static const bool conv_graph = env_is("TTS_ENC_GRAPH", '1');
     if (try_resident) {
         if (!conv_graph) {
             if (tts_status st = enqueue_encoder(e, 1, Lmax, Lmax, s, true)) return st;
@@ -441,7 +418,7 @@ tts_status tts_encoder_run_state(tts_encoder* e, const int32_t* ids, const int32
             }
         }
     }
-    static const bool batch_off = getenv("TTS_ENC_BATCH_RESIDENT") && getenv("TTS_ENC_BATCH_RESIDENT")[0] == '0';  // A/B knob
+    static const bool batch_off = env_is("TTS_ENC_BATCH_RESIDENT", '0');  // A/B knob
     if (e->resident && e->bgran && !skip_resident && B >= 2 && !state_in && !batch_off) {
         // batched resident BiLSTM: the convs + projection graph, then one persistent launch
         auto key = std::make_pair(B, Lmax);

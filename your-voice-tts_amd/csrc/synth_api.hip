@@ -13,10 +13,10 @@
 
 #include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 #include <vector>
 
 #include "common.h"
+#include "host_util.h"
 
 struct tts_synth {
     tts_encoder* e = nullptr;
@@ -102,7 +102,7 @@ tts_status tts_synth_create(tts_encoder* e, tts_decoder* d, tts_postnet* p, tts_
     // +0.2 ms per configs[1] sentence; rocprofv3 SQ counters showed the same busy cycles at 3x the
     // wall time).  TTS_STREAM_PRIO=1 restores the priorities (measurement only).
     int prio_lo = 0, prio_hi = 0;
-    if (const char* v = getenv("TTS_STREAM_PRIO"); v && v[0] == '1')
+    if (tts::env_is("TTS_STREAM_PRIO", '1'))
         if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess) prio_lo = prio_hi = 0;
     if (hipStreamCreateWithPriority(&s->stream, hipStreamNonBlocking, prio_hi) != hipSuccess ||
         hipStreamCreateWithPriority(&s->gl_stream, hipStreamNonBlocking, prio_lo) != hipSuccess ||
@@ -238,10 +238,7 @@ tts_status synth_stages(tts_synth* s, int32_t* h_ids, int32_t* h_lens, const int
     // or against the next call (each record / wait held the GPU ~6 us: the first Griffin-Lim
     // launch waited on the caller's stream, the next call's first launch on the previous call's
     // end-of-run event).  TTS_SYNTH_OWN_STREAM=1 restores the handle's own stream.
-    static const bool own_stream = [] {
-        const char* v = getenv("TTS_SYNTH_OWN_STREAM");
-        return v && v[0] == '1';
-    }();
+    static const bool own_stream = tts::env_is("TTS_SYNTH_OWN_STREAM", '1');
     hipStream_t ss = B == 1 && !own_stream ? cs : s->stream;
     s->last_cs = ss == cs ? cs : nullptr;
     const int cap = max_steps + 21;
@@ -292,10 +289,8 @@ tts_status synth_stages(tts_synth* s, int32_t* h_ids, int32_t* h_lens, const int
     // launch clamps into fspec (a longer sentence makes it an empty run, redone below)
     const int Ts = (int)std::min<size_t>(256, T);
     const int Tp = (int)std::min<size_t>(1024, T);
-    static const bool no_spec = [] {  // measurement only: no speculative Griffin-Lim in the hook
-        const char* v = getenv("TTS_NO_SPEC_GL");
-        return v && v[0] == '1';
-    }();
+    // measurement only: no speculative Griffin-Lim in the hook
+    static const bool no_spec = tts::env_is("TTS_NO_SPEC_GL", '1');
     const bool spec_gl = B == 1 && s->r == 1 && !no_spec && wav_cap >= (int64_t)s->hop * (Ts - 1) &&
                          tts::gl_persistent_path(s->g, 1, Ts, Ts, gl_iters);
     struct Hook {
@@ -348,10 +343,8 @@ tts_status synth_stages(tts_synth* s, int32_t* h_ids, int32_t* h_lens, const int
         tts::encoder_set_defer_status(s->e, est != nullptr);
         tts::decoder_set_pipeline_io(s->d, tts::encoder_lens_buffer(s->e), est, ehost, spec_gl ? s->fspec : nullptr, Ts);
     }
-    static const bool no_hook = [] {  // measurement only: postnet and Griffin-Lim after the host's wait
-        const char* v = getenv("TTS_NO_HOOK");
-        return v && v[0] == '1';
-    }();
+    // measurement only: postnet and Griffin-Lim after the host's wait
+    static const bool no_hook = tts::env_is("TTS_NO_HOOK", '1');
     tts::decoder_set_post_hook(s->d, B == 1 && !no_hook ? +hook_fn : nullptr, &hook);
     for (int attempt = 0;; ++attempt) {
         if ((st = tts_encoder_run(s->e, ids_dev, h_lens, B, Lmax, enc, ss))) return st;

@@ -27,11 +27,11 @@
 #include <map>
 #include <string>
 #include <tuple>
-#include <unordered_map>
 #include <vector>
 
 #include "conv1d.h"
 #include "decoder.h"
+#include "host_util.h"
 #include "sgemm.h"
 #include "resident.h"
 #include "tacotron.h"
@@ -59,11 +59,6 @@ struct Buf {
     size_t n = 0;
 };
 
-struct TGraphs {
-    hipGraphExec_t step[2] = {nullptr, nullptr};
-    hipGraphExec_t chunk = nullptr;
-};
-
 }  // namespace
 
 struct tts_tacotron {
@@ -71,7 +66,7 @@ struct tts_tacotron {
     int nmel = 400, num_chars = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
-    std::vector<void*> allocs;
+    DeviceAllocs dev;
     // encoder
     float *emb = nullptr, *Wep0 = nullptr, *bep0 = nullptr, *Wep1 = nullptr, *bep1 = nullptr, *spk = nullptr;
     Cbhg enc, post;
@@ -97,7 +92,7 @@ struct tts_tacotron {
     int *lens = nullptr, *win_idx = nullptr, *nidx = nullptr, *flag1 = nullptr, *count = nullptr, *done = nullptr;
     int *n_steps = nullptr, *state = nullptr, *host_flags = nullptr;
     float *mel_hist = nullptr, *stop_hist = nullptr, *align_hist = nullptr;
-    std::map<std::tuple<int, int, int>, TGraphs> graphs;
+    std::map<std::tuple<int, int, int>, StepGraphs> graphs;
     // sequence workspace (encoder, GST, postnet), grown on demand
     int *ids = nullptr, *T = nullptr, *spk_ids = nullptr, *gT = nullptr;
     Buf bank, p0, y, hwa, hwb, xi, seq_out, pre_a, pre_b, g0, g1, gxi, gh, gst_out, spk_rows;
@@ -117,15 +112,6 @@ struct tts_tacotron {
 
 namespace {
 
-template <typename T>
-tts_status talloc(tts_tacotron* t, T** p, size_t n) {
-    void* q = nullptr;
-    TTS_HIP(hipMalloc(&q, n * sizeof(T) + 16));
-    t->allocs.push_back(q);
-    *p = static_cast<T*>(q);
-    return TTS_OK;
-}
-
 // grow-only scratch; frees the old buffer after draining the stream that may still read it
 tts_status grow(tts_tacotron* t, Buf& b, size_t n) {
     if (n <= b.n) return TTS_OK;
@@ -137,30 +123,6 @@ tts_status grow(tts_tacotron* t, Buf& b, size_t n) {
     }
     TTS_HIP(hipMalloc(&b.p, n * sizeof(float) + 16));
     b.n = n;
-    return TTS_OK;
-}
-
-struct WeightMap {
-    std::unordered_map<std::string, std::pair<const float*, int64_t>> m;
-    const float* get(const std::string& k, int64_t numel) const {
-        auto it = m.find(k);
-        if (it == m.end()) {
-            set_error("missing weight " + k);
-            return nullptr;
-        }
-        if (numel >= 0 && it->second.second != numel) {
-            set_error("weight " + k + " has " + std::to_string(it->second.second) + " elements, expected " +
-                      std::to_string(numel));
-            return nullptr;
-        }
-        return it->second.first;
-    }
-};
-
-tts_status copy_w(tts_tacotron* t, float** dst, const float* src, size_t n, hipStream_t s) {
-    tts_status st = talloc(t, dst, n);
-    if (st) return st;
-    TTS_HIP(hipMemcpyAsync(*dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     return TTS_OK;
 }
 
@@ -206,8 +168,8 @@ tts_status fold_prenet_bn(tts_tacotron* t, WeightMap& wm, hipStream_t s) {
         GET(mu, p + "bn.running_mean", rows);
         GET(var, p + "bn.running_var", rows);
         float *wf = nullptr, *bf = nullptr;
-        tts_status st = talloc(t, &wf, (size_t)rows * cols);
-        if (!st) st = talloc(t, &bf, rows);
+        tts_status st = t->dev.alloc(&wf, (size_t)rows * cols);
+        if (!st) st = t->dev.alloc(&bf, rows);
         if (st) return st;
         TTS_HIP(fold_linear_bn(it->second.first, b, g, be, mu, var, rows, cols, 1e-5f, wf, bf, s));
         wm.m[p + "linear_layer.weight"] = {wf, (int64_t)rows * cols};
@@ -223,43 +185,37 @@ tts_status make_cbhg(tts_tacotron* t, Cbhg& c, const WeightMap& wm, const std::s
     c.p0 = p0;
     c.p1 = p1;
     const int nb = K * 128;
-    tts_status st;
-#define CK(x)                \
-    do {                     \
-        st = (x);            \
-        if (st) return st;   \
-    } while (0)
-    CK(talloc(t, &c.Wb, (size_t)cin * K * nb));
-    CK(talloc(t, &c.scb, nb));
-    CK(talloc(t, &c.shb, nb));
+    TTS_TRY(t->dev.alloc(&c.Wb, (size_t)cin * K * nb));
+    TTS_TRY(t->dev.alloc(&c.scb, nb));
+    TTS_TRY(t->dev.alloc(&c.shb, nb));
     TTS_HIP(hipMemsetAsync(c.Wb, 0, sizeof(float) * cin * K * nb, s));
     for (int k = 1; k <= K; ++k) {
         const std::string pre = p + ".conv1d_banks." + std::to_string(k - 1);
         GET(w, pre + ".conv1d.weight", (int64_t)128 * cin * k);
         TTS_HIP(conv_pack_bank(w, 128, cin, k, K, (k - 1) * 128, nb, c.Wb, s));
-        CK(fold_bn_key(t, wm, pre + ".bn", nullptr, 128, 1e-3f, c.scb + (k - 1) * 128, c.shb + (k - 1) * 128, s));
+        TTS_TRY(fold_bn_key(t, wm, pre + ".bn", nullptr, 128, 1e-3f, c.scb + (k - 1) * 128, c.shb + (k - 1) * 128, s));
     }
     {
         const std::string pre = p + ".conv1d_projections.0";
         GET(w, pre + ".conv1d.weight", (int64_t)p0 * nb * 3);
-        CK(talloc(t, &c.Wp0, (size_t)nb * 3 * conv_co_pad(p0)));
-        CK(talloc(t, &c.sc0, p0));
-        CK(talloc(t, &c.sh0, p0));
+        TTS_TRY(t->dev.alloc(&c.Wp0, (size_t)nb * 3 * conv_co_pad(p0)));
+        TTS_TRY(t->dev.alloc(&c.sc0, p0));
+        TTS_TRY(t->dev.alloc(&c.sh0, p0));
         TTS_HIP(conv_pack(w, p0, nb, 3, c.Wp0, s));
-        CK(fold_bn_key(t, wm, pre + ".bn", nullptr, p0, 1e-3f, c.sc0, c.sh0, s));
+        TTS_TRY(fold_bn_key(t, wm, pre + ".bn", nullptr, p0, 1e-3f, c.sc0, c.sh0, s));
     }
     {
         const std::string pre = p + ".conv1d_projections.1";
         GET(w, pre + ".conv1d.weight", (int64_t)p1 * p0 * 3);
-        CK(talloc(t, &c.Wp1, (size_t)p0 * 3 * conv_co_pad(p1)));
-        CK(talloc(t, &c.sc1, p1));
-        CK(talloc(t, &c.sh1, p1));
+        TTS_TRY(t->dev.alloc(&c.Wp1, (size_t)p0 * 3 * conv_co_pad(p1)));
+        TTS_TRY(t->dev.alloc(&c.sc1, p1));
+        TTS_TRY(t->dev.alloc(&c.sh1, p1));
         TTS_HIP(conv_pack(w, p1, p0, 3, c.Wp1, s));
-        CK(fold_bn_key(t, wm, pre + ".bn", nullptr, p1, 1e-3f, c.sc1, c.sh1, s));
+        TTS_TRY(fold_bn_key(t, wm, pre + ".bn", nullptr, p1, 1e-3f, c.sc1, c.sh1, s));
     }
     if (p1 != 128) {
         GET(w, p + ".pre_highway.weight", (int64_t)128 * p1);
-        CK(talloc(t, &c.Wph, (size_t)p1 * 128));
+        TTS_TRY(t->dev.alloc(&c.Wph, (size_t)p1 * 128));
         TTS_HIP(linear_pack_as_conv(w, 128, p1, 0, 128, c.Wph, s));
     }
     for (int i = 0; i < 4; ++i) {
@@ -268,17 +224,17 @@ tts_status make_cbhg(tts_tacotron* t, Cbhg& c, const WeightMap& wm, const std::s
         GET(hb, pre + ".H.bias", 128);
         GET(tw, pre + ".T.weight", 128 * 128);
         GET(tb, pre + ".T.bias", 128);
-        CK(talloc(t, &c.Whw[i], (size_t)128 * 256));
-        CK(talloc(t, &c.bhw[i], 256));
+        TTS_TRY(t->dev.alloc(&c.Whw[i], (size_t)128 * 256));
+        TTS_TRY(t->dev.alloc(&c.bhw[i], 256));
         TTS_HIP(linear_pack_strided(hw, 128, 128, 0, 2, 256, c.Whw[i], s));
         TTS_HIP(linear_pack_strided(tw, 128, 128, 1, 2, 256, c.Whw[i], s));
         TTS_HIP(copy_strided(hb, 128, c.bhw[i], 2, s));
         TTS_HIP(copy_strided(tb, 128, c.bhw[i] + 1, 2, s));
     }
-    CK(talloc(t, &c.Wgi, (size_t)128 * 768));
-    CK(talloc(t, &c.bgi, 768));
-    CK(talloc(t, &c.Whh, (size_t)2 * 384 * 128));
-    CK(talloc(t, &c.bhh, 768));
+    TTS_TRY(t->dev.alloc(&c.Wgi, (size_t)128 * 768));
+    TTS_TRY(t->dev.alloc(&c.bgi, 768));
+    TTS_TRY(t->dev.alloc(&c.Whh, (size_t)2 * 384 * 128));
+    TTS_TRY(t->dev.alloc(&c.bhh, 768));
     const char* sfx[2] = {"", "_reverse"};
     for (int d = 0; d < 2; ++d) {
         const std::string pre = p + ".gru.";
@@ -291,7 +247,6 @@ tts_status make_cbhg(tts_tacotron* t, Cbhg& c, const WeightMap& wm, const std::s
         TTS_HIP(hipMemcpyAsync(c.Whh + (size_t)d * 384 * 128, whh, 384 * 128 * sizeof(float), hipMemcpyDeviceToDevice, s));
         TTS_HIP(hipMemcpyAsync(c.bhh + d * 384, bhh, 384 * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
-#undef CK
     return TTS_OK;
 }
 
@@ -608,20 +563,6 @@ tts_status enqueue_step(tts_tacotron* t, int B, int Lmax, int max_steps, int p, 
     return TTS_OK;
 }
 
-tts_status build_graph(tts_tacotron* t, int B, int Lmax, int max_steps, int first_parity, int steps,
-                       hipGraphExec_t* out) {
-    hipGraph_t g = nullptr;
-    TTS_HIP(hipStreamBeginCapture(t->stream, hipStreamCaptureModeThreadLocal));
-    tts_status st = TTS_OK;
-    for (int i = 0; i < steps && st == TTS_OK; ++i) st = enqueue_step(t, B, Lmax, max_steps, (first_parity + i) & 1, t->stream);
-    hipError_t e = hipStreamEndCapture(t->stream, &g);
-    if (st) return st;
-    TTS_HIP(e);
-    TTS_HIP(hipGraphInstantiate(out, g, nullptr, nullptr, 0));
-    TTS_HIP(hipGraphDestroy(g));
-    return TTS_OK;
-}
-
 // step-0 prenet layer 1 on memory_init (later steps get it from launch 9)
 tts_status enqueue_prenet_go(tts_tacotron* t, int B, hipStream_t s) {
     SGemmArgs a{};
@@ -636,30 +577,10 @@ tts_status enqueue_prenet_go(tts_tacotron* t, int B, hipStream_t s) {
     return TTS_OK;
 }
 
-tts_status pack_linear(tts_tacotron* t, const float* W, int N, int K, float** dst, hipStream_t s) {
-    tts_status st = talloc(t, dst, sgemm_packed_floats(N, K));
-    if (st) return st;
-    TTS_HIP(sgemm_pack(W, K, nullptr, 0, N, ROWMAP_IDENTITY, 0, *dst, s));
-    return TTS_OK;
-}
-
-tts_status pack_bias(tts_tacotron* t, const float* a, const float* b, int N, int rowmap, int H, float** dst,
-                     hipStream_t s) {
-    tts_status st = talloc(t, dst, (size_t)(N + 15) / 16 * 16);
-    if (st) return st;
-    TTS_HIP(sgemm_pack_bias(a, b, N, rowmap, H, *dst, s));
-    return TTS_OK;
-}
-
 tts_status create_weights(tts_tacotron* t, const WeightMap& wm, hipStream_t s) {
     const tts_tacotron_config& c = t->cfg;
     const int nmel = t->nmel;
-    tts_status st;
-#define CK(x)              \
-    do {                   \
-        st = (x);          \
-        if (st) return st; \
-    } while (0)
+    tts_status st = TTS_OK;
     // ---- encoder: embedding, prenet, CBHG(K=16, [128, 128])
     {
         auto it = wm.m.find("embedding.weight");
@@ -668,25 +589,25 @@ tts_status create_weights(tts_tacotron* t, const WeightMap& wm, hipStream_t s) {
             return TTS_ERR_INVALID;
         }
         t->num_chars = (int)(it->second.second / 256);
-        CK(copy_w(t, &t->emb, it->second.first, (size_t)t->num_chars * 256, s));
+        TTS_TRY(copy_weight(t->dev, &t->emb, it->second.first, (size_t)t->num_chars * 256, s));
     }
     if (c.num_speakers > 1) {
         GET(w, "speaker_embedding.weight", (int64_t)c.num_speakers * 256);
-        CK(copy_w(t, &t->spk, w, (size_t)c.num_speakers * 256, s));
+        TTS_TRY(copy_weight(t->dev, &t->spk, w, (size_t)c.num_speakers * 256, s));
     }
     {
         GET(w0, "encoder.prenet.layers.0.linear_layer.weight", 256 * 256);
         GET(b0, "encoder.prenet.layers.0.linear_layer.bias", 256);
         GET(w1, "encoder.prenet.layers.1.linear_layer.weight", 128 * 256);
         GET(b1, "encoder.prenet.layers.1.linear_layer.bias", 128);
-        CK(talloc(t, &t->Wep0, (size_t)256 * 256));
-        CK(talloc(t, &t->Wep1, (size_t)256 * 128));
+        TTS_TRY(t->dev.alloc(&t->Wep0, (size_t)256 * 256));
+        TTS_TRY(t->dev.alloc(&t->Wep1, (size_t)256 * 128));
         TTS_HIP(linear_pack_as_conv(w0, 256, 256, 0, 256, t->Wep0, s));
         TTS_HIP(linear_pack_as_conv(w1, 128, 256, 0, 128, t->Wep1, s));
-        CK(copy_w(t, &t->bep0, b0, 256, s));
-        CK(copy_w(t, &t->bep1, b1, 128, s));
+        TTS_TRY(copy_weight(t->dev, &t->bep0, b0, 256, s));
+        TTS_TRY(copy_weight(t->dev, &t->bep1, b1, 128, s));
     }
-    CK(make_cbhg(t, t->enc, wm, "encoder.cbhg.cbhg", 128, 16, 128, 128, s));
+    TTS_TRY(make_cbhg(t, t->enc, wm, "encoder.cbhg.cbhg", 128, 16, 128, 128, s));
     // ---- GST
     if (c.gst) {
         static const int filt[7] = {1, 32, 32, 64, 64, 128, 128};
@@ -695,29 +616,29 @@ tts_status create_weights(tts_tacotron* t, const WeightMap& wm, hipStream_t s) {
             const int64_t n = (int64_t)filt[i + 1] * filt[i] * 9;
             GET(w, pre + ".weight", n);
             GET(bias, pre + ".bias", filt[i + 1]);
-            CK(copy_w(t, &t->gW[i], w, n, s));
-            CK(talloc(t, &t->gsc[i], filt[i + 1]));
-            CK(talloc(t, &t->gsh[i], filt[i + 1]));
-            CK(fold_bn_key(t, wm, "gst.encoder.bns." + std::to_string(i), bias, filt[i + 1], 1e-5f, t->gsc[i], t->gsh[i],
+            TTS_TRY(copy_weight(t->dev, &t->gW[i], w, n, s));
+            TTS_TRY(t->dev.alloc(&t->gsc[i], filt[i + 1]));
+            TTS_TRY(t->dev.alloc(&t->gsh[i], filt[i + 1]));
+            TTS_TRY(fold_bn_key(t, wm, "gst.encoder.bns." + std::to_string(i), bias, filt[i + 1], 1e-5f, t->gsc[i], t->gsh[i],
                            s));
         }
         GET(wih, "gst.encoder.recurrence.weight_ih_l0", 384 * 256);
         GET(whh, "gst.encoder.recurrence.weight_hh_l0", 384 * 128);
         GET(bih, "gst.encoder.recurrence.bias_ih_l0", 384);
         GET(bhh, "gst.encoder.recurrence.bias_hh_l0", 384);
-        CK(talloc(t, &t->gWi, (size_t)256 * 384));
+        TTS_TRY(t->dev.alloc(&t->gWi, (size_t)256 * 384));
         TTS_HIP(linear_pack_as_conv(wih, 384, 256, 0, 384, t->gWi, s));
-        CK(copy_w(t, &t->gbi, bih, 384, s));
-        CK(copy_w(t, &t->gWhh, whh, 384 * 128, s));
-        CK(copy_w(t, &t->gbhh, bhh, 384, s));
+        TTS_TRY(copy_weight(t->dev, &t->gbi, bih, 384, s));
+        TTS_TRY(copy_weight(t->dev, &t->gWhh, whh, 384 * 128, s));
+        TTS_TRY(copy_weight(t->dev, &t->gbhh, bhh, 384, s));
         GET(tok, "gst.style_token_layer.style_tokens", 10 * 64);
         GET(wq, "gst.style_token_layer.attention.W_query.weight", 256 * 128);
         GET(wk, "gst.style_token_layer.attention.W_key.weight", 256 * 64);
         GET(wv, "gst.style_token_layer.attention.W_value.weight", 256 * 64);
-        CK(copy_w(t, &t->tokens, tok, 640, s));
-        CK(copy_w(t, &t->Wsq, wq, 256 * 128, s));
-        CK(copy_w(t, &t->Wsk, wk, 256 * 64, s));
-        CK(copy_w(t, &t->Wsv, wv, 256 * 64, s));
+        TTS_TRY(copy_weight(t->dev, &t->tokens, tok, 640, s));
+        TTS_TRY(copy_weight(t->dev, &t->Wsq, wq, 256 * 128, s));
+        TTS_TRY(copy_weight(t->dev, &t->Wsk, wk, 256 * 64, s));
+        TTS_TRY(copy_weight(t->dev, &t->Wsv, wv, 256 * 64, s));
     }
     // ---- decoder
     {
@@ -727,17 +648,17 @@ tts_status create_weights(tts_tacotron* t, const WeightMap& wm, hipStream_t s) {
         GET(pb1, "decoder.prenet.layers.1.linear_layer.bias", T_PRE2);
         GET(sw, "decoder.stopnet.linear.weight", T_DEC + nmel);
         GET(sb, "decoder.stopnet.linear.bias", 1);
-        CK(pack_linear(t, pw0, T_PRE1, nmel, &t->W_go, s));
-        CK(pack_bias(t, pb0, nullptr, T_PRE1, ROWMAP_IDENTITY, 0, &t->b_go, s));
-        CK(pack_linear(t, pw1, T_PRE2, T_PRE1, &t->W_p2, s));
-        CK(pack_bias(t, pb1, nullptr, T_PRE2, ROWMAP_IDENTITY, 0, &t->b_p2, s));
+        TTS_TRY(pack_linear(t->dev, pw0, T_PRE1, nmel, &t->W_go, s));
+        TTS_TRY(pack_bias(t->dev, pb0, nullptr, T_PRE1, ROWMAP_IDENTITY, 0, &t->b_go, s));
+        TTS_TRY(pack_linear(t->dev, pw1, T_PRE2, T_PRE1, &t->W_p2, s));
+        TTS_TRY(pack_bias(t->dev, pb1, nullptr, T_PRE2, ROWMAP_IDENTITY, 0, &t->b_p2, s));
         float *wf = nullptr, *bf = nullptr;
         const int K = nmel + T_DEC;
         TTS_HIP(hipMalloc(&wf, sizeof(float) * (T_PRE1 + 1) * K));
         TTS_HIP(hipMalloc(&bf, sizeof(float) * (T_PRE1 + 1)));
         hipError_t e = fold_pre1_stop(pw0, pb0, sw, sb, nmel, wf, bf, s);
-        if (e == hipSuccess) st = pack_linear(t, wf, T_PRE1 + 1, K, &t->W_p1s, s);
-        if (e == hipSuccess && !st) st = pack_bias(t, bf, nullptr, T_PRE1 + 1, ROWMAP_IDENTITY, 0, &t->b_p1s, s);
+        if (e == hipSuccess) st = pack_linear(t->dev, wf, T_PRE1 + 1, K, &t->W_p1s, s);
+        if (e == hipSuccess && !st) st = pack_bias(t->dev, bf, nullptr, T_PRE1 + 1, ROWMAP_IDENTITY, 0, &t->b_p1s, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         (void)hipFree(wf);
         (void)hipFree(bf);
@@ -749,75 +670,71 @@ tts_status create_weights(tts_tacotron* t, const WeightMap& wm, hipStream_t s) {
         GET(whh, "decoder.attention_rnn.weight_hh", (int64_t)3 * T_DEC * T_DEC);
         GET(bih, "decoder.attention_rnn.bias_ih", 3 * T_DEC);
         GET(bhh, "decoder.attention_rnn.bias_hh", 3 * T_DEC);
-        CK(talloc(t, &t->W_att, sgemm_packed_floats(4 * T_DEC, T_XA + T_DEC)));
+        TTS_TRY(t->dev.alloc(&t->W_att, sgemm_packed_floats(4 * T_DEC, T_XA + T_DEC)));
         TTS_HIP(sgemm_pack(wih, T_XA, whh, T_DEC, 4 * T_DEC, ROWMAP_GRU, T_DEC, t->W_att, s));
-        CK(pack_bias(t, bih, bhh, 4 * T_DEC, ROWMAP_GRU, T_DEC, &t->b_att, s));
+        TTS_TRY(pack_bias(t->dev, bih, bhh, 4 * T_DEC, ROWMAP_GRU, T_DEC, &t->b_att, s));
     }
     {
         GET(wq, "decoder.attention_layer.query_layer.linear_layer.weight", ADIM * T_DEC);
         GET(win, "decoder.attention_layer.inputs_layer.linear_layer.weight", ADIM * T_DEC);
         GET(vw, "decoder.attention_layer.v.linear_layer.weight", ADIM);
         GET(vb, "decoder.attention_layer.v.linear_layer.bias", 1);
-        CK(pack_linear(t, wq, ADIM, T_DEC, &t->W_q, s));
-        CK(talloc(t, &t->W_qT, (size_t)ADIM * T_DEC));
+        TTS_TRY(pack_linear(t->dev, wq, ADIM, T_DEC, &t->W_q, s));
+        TTS_TRY(t->dev.alloc(&t->W_qT, (size_t)ADIM * T_DEC));
         TTS_HIP(transpose_f32(wq, ADIM, T_DEC, t->W_qT, s));
-        {
-            const char* fq = getenv("TTS_GST_FUSED_QUERY");
-            t->fused_query = !(fq && fq[0] == '0');
-        }
-        CK(copy_w(t, &t->W_in, win, ADIM * T_DEC, s));
-        CK(copy_w(t, &t->v, vw, ADIM, s));
-        CK(copy_w(t, &t->v_b, vb, 1, s));
+        t->fused_query = !env_is("TTS_GST_FUSED_QUERY", '0');
+        TTS_TRY(copy_weight(t->dev, &t->W_in, win, ADIM * T_DEC, s));
+        TTS_TRY(copy_weight(t->dev, &t->v, vw, ADIM, s));
+        TTS_TRY(copy_weight(t->dev, &t->v_b, vb, 1, s));
         if (c.trans_agent) {
             GET(taw, "decoder.attention_layer.ta.weight", 2 * T_DEC);
             GET(tab, "decoder.attention_layer.ta.bias", 1);
-            CK(copy_w(t, &t->ta_w, taw, 2 * T_DEC, s));
-            CK(copy_w(t, &t->ta_b, tab, 1, s));
+            TTS_TRY(copy_weight(t->dev, &t->ta_w, taw, 2 * T_DEC, s));
+            TTS_TRY(copy_weight(t->dev, &t->ta_b, tab, 1, s));
         }
         if (c.location_attn) {
             GET(lcw, "decoder.attention_layer.location_layer.location_conv.weight", NLOC * 2 * KLOC);
             GET(ldw, "decoder.attention_layer.location_layer.location_dense.linear_layer.weight", ADIM * NLOC);
-            CK(copy_w(t, &t->loc_conv, lcw, NLOC * 2 * KLOC, s));
-            CK(copy_w(t, &t->loc_dense, ldw, ADIM * NLOC, s));
+            TTS_TRY(copy_weight(t->dev, &t->loc_conv, lcw, NLOC * 2 * KLOC, s));
+            TTS_TRY(copy_weight(t->dev, &t->loc_dense, ldw, ADIM * NLOC, s));
         }
     }
     {
         GET(pw, "decoder.project_to_decoder_in.weight", T_DEC * 2 * T_DEC);
         GET(pb, "decoder.project_to_decoder_in.bias", T_DEC);
-        CK(pack_linear(t, pw, T_DEC, 2 * T_DEC, &t->W_proj, s));
-        CK(pack_bias(t, pb, nullptr, T_DEC, ROWMAP_IDENTITY, 0, &t->b_proj, s));
+        TTS_TRY(pack_linear(t->dev, pw, T_DEC, 2 * T_DEC, &t->W_proj, s));
+        TTS_TRY(pack_bias(t->dev, pb, nullptr, T_DEC, ROWMAP_IDENTITY, 0, &t->b_proj, s));
         for (int i = 0; i < 2; ++i) {
             const std::string pre = "decoder.decoder_rnns." + std::to_string(i) + ".";
             GET(wih, pre + "weight_ih", 3 * T_DEC * T_DEC);
             GET(whh, pre + "weight_hh", 3 * T_DEC * T_DEC);
             GET(bih, pre + "bias_ih", 3 * T_DEC);
             GET(bhh, pre + "bias_hh", 3 * T_DEC);
-            CK(talloc(t, &t->W_g[i], sgemm_packed_floats(4 * T_DEC, 2 * T_DEC)));
+            TTS_TRY(t->dev.alloc(&t->W_g[i], sgemm_packed_floats(4 * T_DEC, 2 * T_DEC)));
             TTS_HIP(sgemm_pack(wih, T_DEC, whh, T_DEC, 4 * T_DEC, ROWMAP_GRU, T_DEC, t->W_g[i], s));
-            CK(pack_bias(t, bih, bhh, 4 * T_DEC, ROWMAP_GRU, T_DEC, &t->b_g[i], s));
+            TTS_TRY(pack_bias(t->dev, bih, bhh, 4 * T_DEC, ROWMAP_GRU, T_DEC, &t->b_g[i], s));
         }
         GET(mw, "decoder.proj_to_mel.weight", (int64_t)nmel * T_DEC);
         GET(mb, "decoder.proj_to_mel.bias", nmel);
-        CK(pack_linear(t, mw, nmel, T_DEC, &t->W_mel, s));
-        CK(pack_bias(t, mb, nullptr, nmel, ROWMAP_IDENTITY, 0, &t->b_mel, s));
+        TTS_TRY(pack_linear(t->dev, mw, nmel, T_DEC, &t->W_mel, s));
+        TTS_TRY(pack_bias(t->dev, mb, nullptr, nmel, ROWMAP_IDENTITY, 0, &t->b_mel, s));
         GET(ai, "decoder.attention_rnn_init.weight", T_DEC);
         GET(mi, "decoder.memory_init.weight", nmel);
         GET(di, "decoder.decoder_rnn_inits.weight", 2 * T_DEC);
-        CK(copy_w(t, &t->att_init, ai, T_DEC, s));
-        CK(copy_w(t, &t->mem_init, mi, nmel, s));
-        CK(copy_w(t, &t->dec_init, di, 2 * T_DEC, s));
+        TTS_TRY(copy_weight(t->dev, &t->att_init, ai, T_DEC, s));
+        TTS_TRY(copy_weight(t->dev, &t->mem_init, mi, nmel, s));
+        TTS_TRY(copy_weight(t->dev, &t->dec_init, di, 2 * T_DEC, s));
     }
     // ---- PostCBHG(K=8, [256, 80]) + last_linear
-    CK(make_cbhg(t, t->post, wm, "postnet.cbhg", 80, 8, 256, 80, s));
+    TTS_TRY(make_cbhg(t, t->post, wm, "postnet.cbhg", 80, 8, 256, 80, s));
     {
         GET(lw, "last_linear.0.weight", (int64_t)NLIN * 256);
         GET(lb, "last_linear.0.bias", NLIN);
-        CK(talloc(t, &t->W_ll, (size_t)256 * conv_co_pad(NLIN)));
+        TTS_TRY(t->dev.alloc(&t->W_ll, (size_t)256 * conv_co_pad(NLIN)));
         TTS_HIP(hipMemsetAsync(t->W_ll, 0, sizeof(float) * 256 * conv_co_pad(NLIN), s));
         TTS_HIP(linear_pack_as_conv(lw, NLIN, 256, 0, conv_co_pad(NLIN), t->W_ll, s));
-        CK(copy_w(t, &t->b_ll, lb, NLIN, s));
+        TTS_TRY(copy_weight(t->dev, &t->b_ll, lb, NLIN, s));
     }
-#undef CK
     return TTS_OK;
 }
 
@@ -827,45 +744,38 @@ tts_status create_workspace(tts_tacotron* t, hipStream_t s) {
     t->Bcap = Bc;
     t->Lcap = Lc;
     t->hist_cap = c.max_steps + 1;
-    tts_status st;
-#define CK(x)              \
-    do {                   \
-        st = (x);          \
-        if (st) return st; \
-    } while (0)
-    CK(talloc(t, &t->denc, (size_t)Bc * Lc * T_DEC));
-    CK(talloc(t, &t->Pt, (size_t)Bc * ADIM * Lc));
-    CK(talloc(t, &t->h_att, (size_t)2 * Bc * T_DEC));
-    CK(talloc(t, &t->h1, (size_t)2 * Bc * T_DEC));
-    CK(talloc(t, &t->h2, (size_t)2 * Bc * T_DEC));
-    CK(talloc(t, &t->xa, (size_t)2 * Bc * T_XA));
-    CK(talloc(t, &t->mem, (size_t)Bc * t->nmel));
-    CK(talloc(t, &t->pre1, (size_t)Bc * T_PRE1));
-    CK(talloc(t, &t->q, (size_t)Bc * ADIM));
-    CK(talloc(t, &t->din, (size_t)Bc * T_DEC));
-    CK(talloc(t, &t->d1, (size_t)Bc * T_DEC));
-    CK(talloc(t, &t->d2, (size_t)Bc * T_DEC));
-    CK(talloc(t, &t->alpha, (size_t)Bc * Lc));
-    CK(talloc(t, &t->att_w, (size_t)Bc * Lc));
-    CK(talloc(t, &t->att_cum, (size_t)Bc * Lc));
-    CK(talloc(t, &t->u, Bc));
-    CK(talloc(t, &t->tail, Bc));
-    CK(talloc(t, &t->lens, Bc));
-    CK(talloc(t, &t->win_idx, Bc));
-    CK(talloc(t, &t->nidx, Bc));
-    CK(talloc(t, &t->flag1, Bc));
-    CK(talloc(t, &t->count, Bc));
-    CK(talloc(t, &t->done, Bc));
-    CK(talloc(t, &t->n_steps, Bc));
-    CK(talloc(t, &t->state, 8));  // {step, n_active} x 2 parities, stop_acc
-    CK(talloc(t, &t->mel_hist, (size_t)Bc * t->hist_cap * t->nmel));
-    CK(talloc(t, &t->stop_hist, (size_t)Bc * t->hist_cap));
-    CK(talloc(t, &t->align_hist, (size_t)Bc * t->hist_cap * Lc));
-    CK(talloc(t, &t->ids, (size_t)Bc * std::max(Lc, 1)));
-    CK(talloc(t, &t->T, Bc));
-    CK(talloc(t, &t->spk_ids, Bc));
-    CK(talloc(t, &t->gT, Bc));
-#undef CK
+    TTS_TRY(t->dev.alloc(&t->denc, (size_t)Bc * Lc * T_DEC));
+    TTS_TRY(t->dev.alloc(&t->Pt, (size_t)Bc * ADIM * Lc));
+    TTS_TRY(t->dev.alloc(&t->h_att, (size_t)2 * Bc * T_DEC));
+    TTS_TRY(t->dev.alloc(&t->h1, (size_t)2 * Bc * T_DEC));
+    TTS_TRY(t->dev.alloc(&t->h2, (size_t)2 * Bc * T_DEC));
+    TTS_TRY(t->dev.alloc(&t->xa, (size_t)2 * Bc * T_XA));
+    TTS_TRY(t->dev.alloc(&t->mem, (size_t)Bc * t->nmel));
+    TTS_TRY(t->dev.alloc(&t->pre1, (size_t)Bc * T_PRE1));
+    TTS_TRY(t->dev.alloc(&t->q, (size_t)Bc * ADIM));
+    TTS_TRY(t->dev.alloc(&t->din, (size_t)Bc * T_DEC));
+    TTS_TRY(t->dev.alloc(&t->d1, (size_t)Bc * T_DEC));
+    TTS_TRY(t->dev.alloc(&t->d2, (size_t)Bc * T_DEC));
+    TTS_TRY(t->dev.alloc(&t->alpha, (size_t)Bc * Lc));
+    TTS_TRY(t->dev.alloc(&t->att_w, (size_t)Bc * Lc));
+    TTS_TRY(t->dev.alloc(&t->att_cum, (size_t)Bc * Lc));
+    TTS_TRY(t->dev.alloc(&t->u, Bc));
+    TTS_TRY(t->dev.alloc(&t->tail, Bc));
+    TTS_TRY(t->dev.alloc(&t->lens, Bc));
+    TTS_TRY(t->dev.alloc(&t->win_idx, Bc));
+    TTS_TRY(t->dev.alloc(&t->nidx, Bc));
+    TTS_TRY(t->dev.alloc(&t->flag1, Bc));
+    TTS_TRY(t->dev.alloc(&t->count, Bc));
+    TTS_TRY(t->dev.alloc(&t->done, Bc));
+    TTS_TRY(t->dev.alloc(&t->n_steps, Bc));
+    TTS_TRY(t->dev.alloc(&t->state, 8));  // {step, n_active} x 2 parities, stop_acc
+    TTS_TRY(t->dev.alloc(&t->mel_hist, (size_t)Bc * t->hist_cap * t->nmel));
+    TTS_TRY(t->dev.alloc(&t->stop_hist, (size_t)Bc * t->hist_cap));
+    TTS_TRY(t->dev.alloc(&t->align_hist, (size_t)Bc * t->hist_cap * Lc));
+    TTS_TRY(t->dev.alloc(&t->ids, (size_t)Bc * std::max(Lc, 1)));
+    TTS_TRY(t->dev.alloc(&t->T, Bc));
+    TTS_TRY(t->dev.alloc(&t->spk_ids, Bc));
+    TTS_TRY(t->dev.alloc(&t->gT, Bc));
     TTS_HIP(attention_prepare(Lc, c.location_attn));
     TTS_HIP(hipMemsetAsync(t->xa, 0, sizeof(float) * 2 * Bc * T_XA, s));
     TTS_HIP(hipMemsetAsync(t->d2, 0, sizeof(float) * Bc * T_DEC, s));
@@ -881,11 +791,10 @@ tts_status create_workspace(tts_tacotron* t, hipStream_t s) {
 // the reference tensors (the kernel picks its rows at launch).
 tts_status create_resident(tts_tacotron* t, const WeightMap& wm, hipStream_t s) {
     const tts_tacotron_config& c = t->cfg;
-    const char* env = getenv("TTS_RESIDENT");
     int dev = 0, ncu = 0, rate_khz = 0;
     if (!(c.attn_norm == 1 && c.forward_attn && !c.trans_agent && !c.forward_attn_mask && !c.location_attn &&
           !c.windowing && t->nmel <= TR_NMEL_MAX && c.max_steps <= 1000) ||
-        (env && env[0] == '0') || hipGetDevice(&dev) != hipSuccess ||
+        env_is("TTS_RESIDENT", '0') || hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < TR_CUS ||
         hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || rate_khz <= 0 ||
         tres_prepare() != hipSuccess)
@@ -897,7 +806,7 @@ tts_status create_resident(tts_tacotron* t, const WeightMap& wm, hipStream_t s) 
     do {                                      \
         GET(src_, key, n);                    \
         float* d_ = nullptr;                  \
-        if ((st = copy_w(t, &d_, src_, (size_t)(n), s))) return st; \
+        if ((st = copy_weight(t->dev, &d_, src_, (size_t)(n), s))) return st; \
         dst = d_;                             \
     } while (0)
     CPY(a.a_wih, "decoder.attention_rnn.weight_ih", (int64_t)3 * T_DEC * T_XA);
@@ -925,7 +834,7 @@ tts_status create_resident(tts_tacotron* t, const WeightMap& wm, hipStream_t s) 
 #undef CPY
     a.v = t->v;
     a.v_b = t->v_b;
-    if ((st = talloc(t, &t->tr_gran, tres_granules() + 2))) return st;
+    if ((st = t->dev.alloc(&t->tr_gran, tres_granules() + 2))) return st;
     TTS_HIP(hipMemsetAsync(t->tr_gran, 0, sizeof(unsigned long long) * (tres_granules() + 2), s));
     t->res_ticks = (long long)rate_khz * 50;  // 50 ms per hand-off wait
     // fault injection for the timeout fallback test (TTS_DEC_WAIT_TICKS wall-clock ticks)
@@ -943,10 +852,8 @@ extern "C" {
 void tts_tacotron_destroy(tts_tacotron* t) {
     if (!t) return;
     if (t->stream) (void)hipStreamSynchronize(t->stream);
-    for (auto& kv : t->graphs)
-        for (auto* x : {kv.second.step[0], kv.second.step[1], kv.second.chunk})
-            if (x) (void)hipGraphExecDestroy(x);
-    for (void* p : t->allocs) (void)hipFree(p);
+    for (auto& kv : t->graphs) destroy_step_graphs(kv.second);
+    t->dev.free_all();
     for (Buf* b : {&t->bank, &t->p0, &t->y, &t->hwa, &t->hwb, &t->xi, &t->seq_out, &t->pre_a, &t->pre_b, &t->g0, &t->g1,
                    &t->gxi, &t->gh, &t->gst_out, &t->spk_rows})
         if (b->p) (void)hipFree(b->p);
@@ -987,8 +894,7 @@ tts_status tts_tacotron_create(const tts_tacotron_config* cfg, const tts_tensor*
         set_error("stream/event creation failed");
         return fail(TTS_ERR_HIP);
     }
-    WeightMap wm;
-    for (int i = 0; i < n_tensors; ++i) wm.m[tensors[i].key] = {tensors[i].data, tensors[i].numel};
+    WeightMap wm(tensors, n_tensors);
     tts_status st = fold_prenet_bn(t, wm, s);
     if (!st) st = create_weights(t, wm, s);
     if (!st) st = create_workspace(t, s);
@@ -1131,10 +1037,8 @@ tts_status tts_tacotron_decode(tts_tacotron* t, const float* enc, const int32_t*
         }
         a.salt = t->res_salt;
         a.timeout_ticks = t->res_ticks;
-        static const int taco_first_sleep = [] {
-            const char* v = getenv("TTS_TACO_FIRST_SLEEP");
-            return v ? atoi(v) : 4;  // round 6: configs[4] 1.603M -> 1.615M (tools/taco_sleep_sweep.sh)
-        }();
+        // default 4, round 6: configs[4] 1.603M -> 1.615M (tools/taco_sleep_sweep.sh)
+        static const int taco_first_sleep = env_int("TTS_TACO_FIRST_SLEEP", 4);
         a.first_sleep = taco_first_sleep;
         a.prof = nullptr;
         t->last_ra = a;
@@ -1172,37 +1076,22 @@ tts_status tts_tacotron_decode(tts_tacotron* t, const float* enc, const int32_t*
     auto key = std::make_tuple(B, Lmax, max_steps);
     auto it = t->graphs.find(key);
     if (it == t->graphs.end()) {
-        TGraphs g;
-        tts_status st = build_graph(t, B, Lmax, max_steps, 0, 1, &g.step[0]);
-        if (!st) st = build_graph(t, B, Lmax, max_steps, 1, 1, &g.step[1]);
-        if (!st) st = build_graph(t, B, Lmax, max_steps, 0, TCHUNK, &g.chunk);
+        StepGraphs g;
+        tts_status st = build_step_graphs(
+            g, TCHUNK, t->stream, [&](int p) { return enqueue_step(t, B, Lmax, max_steps, p, t->stream); });
         if (st) return st;
         it = t->graphs.emplace(key, g).first;
     }
-    const TGraphs& g = it->second;
+    const StepGraphs& g = it->second;
     TTS_HIP(hipEventRecord(t->ev_t0, s));
-    auto launch_steps = [&](int n) -> tts_status {
-        while (n > 0) {
-            if ((run & 1) == 0 && n >= TCHUNK) {
-                TTS_HIP(hipGraphLaunch(g.chunk, s));
-                run += TCHUNK;
-                n -= TCHUNK;
-            } else {
-                TTS_HIP(hipGraphLaunch(g.step[run & 1], s));
-                ++run;
-                --n;
-            }
-        }
-        return TTS_OK;
-    };
-    tts_status st = launch_steps(first);
+    tts_status st = launch_steps(g, TCHUNK, run, first, s);
     if (st) return st;
     for (;;) {
         TTS_HIP(hipMemcpyAsync(t->host_flags, t->state + 2 * (run & 1), 2 * sizeof(int), hipMemcpyDeviceToHost, s));
         TTS_HIP(hipStreamSynchronize(s));
         if (t->host_flags[1] == 0) break;
         TTS_CHECK(run <= max_steps + 1, TTS_ERR_HIP, "decoder did not stop within max_steps + 1 (internal error)");
-        st = launch_steps(TCHUNK);
+        st = launch_steps(g, TCHUNK, run, TCHUNK, s);
         if (st) return st;
     }
     TTS_HIP(hipEventRecord(t->ev_t1, s));
