@@ -302,9 +302,14 @@ tts_status tts_synth_sync(tts_synth* s);
 /* ---------------------------------------------------------------- Tacotron / TacotronGST
  * SURVEY config 5 (config_tacotron_gst.json) and config_tacotron.json: the r-frames-per-step
  * Tacotron family, models/tacotron.py / models/tacotrongst.py. */
+/* Longest decoder memory queue, in frames: the prenet reads 80 * memory_size values
+ * (layers/tacotron.py:279-287), at most 1280. */
+#define TTS_TACOTRON_MEMORY_SIZE_MAX 16
 typedef struct tts_tacotron_config {
     int r;                 /* frames per step                                                  */
-    int memory_size;       /* decoder memory queue (<= 0 means r); only memory_size == r       */
+    int memory_size;       /* decoder memory queue in frames (<= 0 means r): r <= memory_size  */
+                           /* <= TTS_TACOTRON_MEMORY_SIZE_MAX; a shorter queue is INVALID (the */
+                           /* reference cannot run it either)                                  */
     int attn_norm;         /* 0 = softmax, 1 = sigmoid                                         */
     int forward_attn, trans_agent, forward_attn_mask, location_attn, windowing;
     int gst;               /* 1: TacotronGST (gst.* weights present), 0: Tacotron              */
@@ -342,6 +347,18 @@ tts_status tts_tacotron_decode(tts_tacotron* t, const float* enc, const int32_t*
                                int max_steps, int steps_cap, float* mel, float* stop, float* align,
                                int32_t* n_steps, void* stream);
 
+/* Replaces Decoder.forward(inputs, memory, mask) (layers/tacotron.py:406-437) in eval mode: step t
+ * decodes from memory_init (t = 0), then the queue updated with teacher row t-1 (80*r values); no stop
+ * rule, exactly `steps` steps per sentence, each at its own encoder length.
+ *   memories [dev] fp32 [B][mem_ldb], row t at t*80*r;  mel [dev] fp32 [B][steps][80*r];
+ *   stop [dev] fp32 [B][steps] stopnet LOGITS;  align [dev] fp32 [B][steps][Lmax] or NULL.
+ * steps <= max_steps + 1 (the history capacity); mem_ldb >= (steps - 1) * 80 * r: teacher rows
+ * 0 .. steps-2 are read, the last row feeds no step and is never touched (it may be absent).  Every attention configuration and memory_size; always the multi-launch path
+ * (tts_tacotron_last_path reports 0).  Returns after the steps have run. */
+tts_status tts_tacotron_decode_teacher(tts_tacotron* t, const float* enc, const int32_t* lens, int B, int Lmax,
+                                       const float* memories, int64_t mem_ldb, int steps, float* mel,
+                                       float* stop, float* align, void* stream);
+
 /* Replaces PostCBHG + last_linear + sigmoid (layers/tacotron.py:246-259, models/tacotrongst.py:43-45,
  * 77-78): mel [dev] fp32 [B][Tmax][80], T [host] int32 [B] -> linear [dev] fp32 [B][Tmax][1025]
  * (rows past T[b] zero). */
@@ -353,7 +370,8 @@ tts_status tts_tacotron_last_timing(tts_tacotron* t, float* loop_ms, int* steps_
 /* Which implementation ran the last tts_tacotron_decode (no reference counterpart): *resident = 1
  * for the resident single-launch decoder (each XCD holds the step weights on its 32 compute units
  * and decodes up to 4 sentences; hand-offs stay inside the XCD), 0 for the per-step multi-launch
- * hipGraph path.  The resident path serves B <= 32, Lmax <= 256, r <= 6, max_steps <= 1000 under
+ * hipGraph path.  The resident path serves B <= 32, Lmax <= 256, a memory queue of
+ * 80 * memory_size <= 512 values (r <= memory_size <= 6), max_steps <= 1000 under
  * config_tacotron_gst.json's attention (sigmoid norm, forward attention without the eval mask, no
  * transition agent / location / windowing) on a GPU with >= 256 compute units; TTS_RESIDENT=0 in
  * the environment at tts_tacotron_create disables it.  A resident run whose hand-off wait timed

@@ -33,6 +33,7 @@ EXPORTS = (
     "tts_gl_draw_phases", "tts_gl_save_pcm16",
     "tts_synth_create", "tts_synth_destroy", "tts_synth_run", "tts_synth_sync",
     "tts_tacotron_create", "tts_tacotron_destroy", "tts_tacotron_encode", "tts_tacotron_decode",
+    "tts_tacotron_decode_teacher",
     "tts_tacotron_postnet", "tts_tacotron_last_timing", "tts_tacotron_last_path", "tts_tacotron_resident_phases",
     "tts_tacotron_profile",
     "tts_last_error", "tts_version",
@@ -130,6 +131,8 @@ def _declare(lib):
     lib.tts_tacotron_encode.argtypes = [vp, vp, I32P, ctypes.c_int, ctypes.c_int, I32P, vp, ctypes.c_int, vp, vp]
     lib.tts_tacotron_decode.argtypes = [vp, vp, I32P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp,
                                         vp, I32P, vp]
+    lib.tts_tacotron_decode_teacher.argtypes = [vp, vp, I32P, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int64,
+                                                ctypes.c_int, vp, vp, vp, vp]
     lib.tts_tacotron_postnet.argtypes = [vp, vp, I32P, ctypes.c_int, ctypes.c_int, vp, vp]
     lib.tts_tacotron_last_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]
     lib.tts_tacotron_last_path.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]

@@ -64,7 +64,10 @@ enum Role {
     ROLE_ENC_LSTM = 6,
     // Tacotron / TacotronGST decoder step (tacotron_api.hip)
     ROLE_T_PRENET1 = 7, ROLE_T_PRENET2 = 8, ROLE_T_ATT_GRU = 9, ROLE_T_QUERY = 10, ROLE_T_PROJ = 11,
-    ROLE_T_DEC_GRU = 12, ROLE_T_MEL = 13, ROLE_T_PRE1_STOP = 14
+    ROLE_T_DEC_GRU = 12, ROLE_T_MEL = 13, ROLE_T_PRE1_STOP = 14,
+    // ROLE_T_PRE1_STOP over the memory queue (memory_size > r, teacher forcing): seg[0] is a window
+    // of a per-sentence sequence that moves MelFused::win floats per step
+    ROLE_T_PRE1_STOP_Q = 15
 };
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_SIGMOID = 2 };
 
@@ -75,10 +78,14 @@ enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_SIGMOID = 2 };
 // using weights folded at load time: W1' = W1 W_mel, w_stop' = [w_s_h | 0] + w_s_mel W_mel.
 // The Tacotron decoder uses it with nmel = 0 over x = [mel out | decoder out] (its mel has a
 // sigmoid, so nothing folds): rows [0, 256) = [W1 | 0], row 256 = the stopnet, rule = 1.
+// With a memory queue (ROLE_T_PRE1_STOP_Q) x = [queue | decoder out] or, teacher forced,
+// [teacher queue | decoder out | mel out]; the queue is the window of [memory_init | frames] that
+// the NEXT step's prenet reads, so its start follows the device step word (MelFused::win).
 struct MelFused {
     int nmel;
     float* pre1;
     int ldp;
+    int win;  // ROLE_T_PRE1_STOP_Q: seg[0] starts min(step + 1, hist_cap) * win floats past its pointer
     float* stop_hist;
     int64_t stop_ldb;
     const int* lens;

@@ -203,6 +203,13 @@ __device__ __forceinline__ void sgemm_body(const SGemmArgs& a) {
 #pragma unroll
     for (int mt = 0; mt < NT; ++mt) xa.row[mt] = FRAG ? ((m0 >> 4) + mt) * 256 : min(m0 + mt * 16 + xrow, a.B - 1);
     xa.xk = FRAG ? 4 * lane : xk;
+    if (ROLE == ROLE_T_PRE1_STOP_Q) {
+        // memory queue: the window the next step's prenet reads starts (step + 1) frames into the
+        // sentence's [memory_init | frames] sequence; this launch waits for the step word before
+        // its activation loads (steps past the end keep counting: clamped to the history)
+        const int t1 = min(__builtin_amdgcn_readfirstlane(st_x) + 1, a.hist_cap);
+        xa.p0 += (int64_t)t1 * a.mf.win;
+    }
 
     floatx4 acc[2][NT];  // MFMA accumulators (see sg_mfma)
 #pragma unroll
@@ -611,6 +618,7 @@ hipError_t sgemm_launch(const SGemmArgs& a, int role, hipStream_t s) {
         case ROLE_T_DEC_GRU: return launch_role<EPI_GRU, ROLE_T_DEC_GRU>(a, s);
         case ROLE_T_MEL: return launch_role<EPI_LINEAR, ROLE_T_MEL>(a, s);
         case ROLE_T_PRE1_STOP: return launch_role<EPI_MEL_FUSED, ROLE_T_PRE1_STOP>(a, s);
+        case ROLE_T_PRE1_STOP_Q: return launch_role<EPI_MEL_FUSED, ROLE_T_PRE1_STOP_Q>(a, s);
         default: return hipErrorInvalidValue;
     }
 }

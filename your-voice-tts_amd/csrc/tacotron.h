@@ -43,6 +43,11 @@ struct TInitArgs {
     int *win_idx, *nidx;
     float* tail;
     int *flag1, *count, *done, *n_steps, *state;
+    // memory queue (memory_size > r): sentence b's queue at step 0, queue[b * queue_ld + k] =
+    // memory_init[k] for k < nq; null with memory_size == r (the go step then reads `mem`)
+    float* queue;
+    int64_t queue_ld;
+    int nq;
 };
 hipError_t launch_tacotron_init(const TInitArgs& a, hipStream_t s);
 
@@ -56,11 +61,16 @@ hipError_t launch_style_attention(const float* h, const float* tokens, const flo
                                   const float* Wv, float* out, int B, hipStream_t s);
 // out[b][:] = table[ids[b]][:] (speaker embedding rows)
 hipError_t launch_gather_rows(const float* table, const int* ids, int width, float* out, int B, hipStream_t s);
-// logical weights [257][nmel + 256] of the [prenet L1 | stopnet] GEMM over x = [mel out | decoder out]:
-// rows n < 256 = [W1[n] | 0], row 256 = [w_stop[256:] | w_stop[:256]] (stopnet input is
+// logical weights [257][nq + 256] of the [prenet L1 | stopnet] GEMM over x = [queue | decoder out],
+// the queue (nq = 80 * memory_size values, layers/tacotron.py:396-404) ending in this step's mel
+// output (nmel = 80 * r values; nq == nmel: x = [mel out | decoder out]):
+// rows n < 256 = [W1[n] | 0], row 256 = [0 | w_stop[256:] | w_stop[:256]] (stopnet input is
 // cat([decoder_output, output]), layers/tacotron.py:388); biases [b1 | b_stop].
-hipError_t fold_pre1_stop(const float* W1, const float* b1, const float* ws, const float* bs, int nmel, float* Wf,
-                          float* bf, hipStream_t s);
+// split_out (teacher forcing: the queue holds teacher frames, not the output): [257][nq + 256 + nmel]
+// over x = [queue | decoder out | mel out], rows n < 256 = [W1[n] | 0 | 0], row 256 =
+// [0 | w_stop[:256] | w_stop[256:]].
+hipError_t fold_pre1_stop(const float* W1, const float* b1, const float* ws, const float* bs, int nmel, int nq,
+                          int split_out, float* Wf, float* bf, hipStream_t s);
 hipError_t launch_fill_int(int* p, int n, int v, hipStream_t s);
 
 }  // namespace tts
@@ -72,8 +82,8 @@ namespace tts {
 // Each XCD runs its own group of up to TR_SPX sentences with a full copy of the step weights held
 // on chip by its 32 CUs (6.7 MB per XCD: 106 VGPRs per thread); every hand-off stays inside the
 // XCD.  Scope: the fast attention configuration (sigmoid norm, forward attention without the eval
-// mask, no location / windowing / transition agent), memory_size == r, B <= 32, L <= 256,
-// nmel <= 512, max_steps <= 1000.
+// mask, no location / windowing / transition agent), a memory queue of 80 * memory_size <= 512
+// values (memory_size >= r), B <= 32, L <= 256, max_steps <= 1000.
 constexpr int TR_CUS = 256, TR_THREADS = 512, TR_WAVES = TR_THREADS / 64;
 constexpr int TR_SPX = 4;                    // sentences per XCD group
 constexpr int TR_GROUPS = 8;                 // XCD groups
@@ -81,7 +91,7 @@ constexpr int TR_RANKS = 32;                 // CUs per group doing work
 constexpr int TR_CPS = TR_RANKS / TR_SPX;    // attention CUs per sentence (positions split 8 ways)
 constexpr int TR_PPC = 32;                   // encoder positions per attention CU (L <= 256)
 constexpr int TR_LMAX = TR_CPS * TR_PPC;
-constexpr int TR_NMEL_MAX = 512;
+constexpr int TR_NMEL_MAX = 512;             // widest prenet layer-1 input: the memory queue, 80 * memory_size
 constexpr int TR_STATUS_PLACEMENT = 50;      // an XCD holds fewer than TR_RANKS workgroups
 constexpr int TR_PHASES = 16;                // phase timers (tts_tacotron_resident_phases)
 
@@ -112,6 +122,11 @@ struct TResArgs {
     long long timeout_ticks;
     int first_sleep;  // s_sleep(1) count before a hand-off's first poll (TTS_TACO_FIRST_SLEEP)   // wall_clock64 ticks per wait
     long long* prof;           // null, or [2][TR_PHASES] phase ticks of CUs 0 and 1 of XCD 0 (measurement)
+    // memory queue (nq != nmel selects the queue instantiation): w_pre1 is [256][nq], sentence b's
+    // history row t is mel_hist[b * hist_ld + t * nmel]
+    int nq;                    // 80 * memory_size, nmel <= nq <= TR_NMEL_MAX
+    const float* mem_init;     // [nq] memory_init
+    int64_t hist_ld;
 };
 size_t tres_granules();
 size_t tres_smem_bytes();

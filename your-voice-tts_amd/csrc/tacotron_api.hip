@@ -21,6 +21,10 @@
 //   prenet L2 -> attention GRU -> query -> attention (256-wide instance) -> project_to_decoder_in
 //   -> decoder GRU 1 (+res) -> decoder GRU 2 (+res) -> proj_to_mel + sigmoid (history, memory)
 //   -> [next step's prenet L1 | stopnet + stop rule] (one GEMM over [mel out | decoder out]).
+// With a memory queue (memory_size > r, :279-287, 396-404) the last launch reads the queue as a
+// window over the sentence's [memory_init | frame history] (tts_tacotron::queue0), so nothing is
+// shifted; tts_tacotron_decode_teacher (Decoder.forward, :406-437) runs the same launches with the
+// teacher frames in the history's place and the stop rule off.
 // The stop rule (t > L/4 and (stop > 0.6 or alpha[L-1] > 0.6), or t > max_decoder_steps) runs per
 // sentence on the device; the host synchronises once per chunk.
 #include <algorithm>
@@ -42,6 +46,14 @@ namespace {
 
 constexpr int NLIN = 1025;  // linear_dim
 constexpr int TCHUNK = 16;  // decoder steps per chunk graph
+constexpr int NQ_MAX = 80 * TTS_TACOTRON_MEMORY_SIZE_MAX;  // widest memory queue (the batch-1 GEMM covers K <= 2560)
+
+// Teacher forcing (tts_tacotron_decode_teacher): the step's mel rows go straight to the caller's
+// buffer, because the history holds the teacher frames the queue reads.
+struct TeacherOut {
+    float* mel;
+    int steps;
+};
 
 struct Cbhg {
     int K = 0, cin = 0, p0 = 0, p1 = 0;
@@ -64,6 +76,7 @@ struct Buf {
 struct tts_tacotron {
     tts_tacotron_config cfg{};
     int nmel = 400, num_chars = 0;
+    int nq = 400;  // memory queue width 80 * memory_size >= nmel (layers/tacotron.py:279-287, 310)
     hipStream_t stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
     DeviceAllocs dev;
@@ -76,7 +89,8 @@ struct tts_tacotron {
     float *tokens = nullptr, *Wsq = nullptr, *Wsk = nullptr, *Wsv = nullptr;
     // decoder, packed (sgemm.h fragment order)
     float *W_go = nullptr, *b_go = nullptr;    // prenet L1 alone (step 0)
-    float *W_p1s = nullptr, *b_p1s = nullptr;  // [prenet L1 | stopnet] over [mel out | decoder out]
+    float *W_p1s = nullptr, *b_p1s = nullptr;  // [prenet L1 | stopnet] over [queue (ends in mel out) | decoder out]
+    float* W_p1t = nullptr;                    // teacher forcing: over [teacher queue | decoder out | mel out]
     float *W_p2 = nullptr, *b_p2 = nullptr, *W_att = nullptr, *b_att = nullptr, *W_q = nullptr;
     float* W_qT = nullptr;  // query_layer weight transposed [256][128]: the attention launch computes the query
     bool fused_query = true;  // TTS_GST_FUSED_QUERY=0: the separate query GEMM launch (A/B)
@@ -92,6 +106,11 @@ struct tts_tacotron {
     int *lens = nullptr, *win_idx = nullptr, *nidx = nullptr, *flag1 = nullptr, *count = nullptr, *done = nullptr;
     int *n_steps = nullptr, *state = nullptr, *host_flags = nullptr;
     float *mel_hist = nullptr, *stop_hist = nullptr, *align_hist = nullptr;
+    // Memory queue: sentence b's frames are mel_hist[b * hist_ld + t * nmel], and the nq floats before
+    // frame 0 are its memory_init (memory_size > r; with memory_size == r nothing reads them), so
+    // step t's queue is the window of nq floats at queue0 + b * hist_ld + t * nmel: no shifting copy.
+    float* queue0 = nullptr;
+    int64_t hist_ld = 0;
     std::map<std::tuple<int, int, int>, StepGraphs> graphs;
     // sequence workspace (encoder, GST, postnet), grown on demand
     int *ids = nullptr, *T = nullptr, *spk_ids = nullptr, *gT = nullptr;
@@ -422,7 +441,7 @@ tts_status run_gst(tts_tacotron* t, const float* style_mel, int Ts, int B, hipSt
 
 // Launches of one decoder step of parity p; `ev` (optional, 10 events) brackets every launch.
 tts_status enqueue_step(tts_tacotron* t, int B, int Lmax, int max_steps, int p, hipStream_t s,
-                        hipEvent_t* ev = nullptr) {
+                        hipEvent_t* ev = nullptr, const TeacherOut* tf = nullptr) {
     int mark = 0;
 #define MARK() \
     if (ev) TTS_HIP(hipEventRecord(ev[mark++], s));
@@ -535,7 +554,8 @@ tts_status enqueue_step(tts_tacotron* t, int B, int Lmax, int max_steps, int p, 
         a.nseg = 1;
         a.W = t->W_mel; a.K = T_DEC; a.N = nmel; a.bias = t->b_mel; a.act = ACT_SIGMOID;
         a.out = t->mem; a.ldo = nmel;
-        a.hist = t->mel_hist; a.ldh = (int64_t)t->hist_cap * nmel; a.hist_cap = t->hist_cap;
+        a.hist = t->mel_hist; a.ldh = t->hist_ld; a.hist_cap = t->hist_cap;
+        if (tf) { a.hist = tf->mel; a.ldh = (int64_t)tf->steps * nmel; a.hist_cap = tf->steps; }
         MARK();
         TTS_HIP(sgemm_launch(a, ROLE_T_MEL, s));
     }
@@ -545,7 +565,23 @@ tts_status enqueue_step(tts_tacotron* t, int B, int Lmax, int max_steps, int p, 
         a.seg[1] = Seg{t->d2, T_DEC, T_DEC};
         a.nseg = 2;
         a.W = t->W_p1s; a.K = nmel + T_DEC; a.N = T_PRE1 + 1; a.bias = t->b_p1s;
-        a.hist = t->mel_hist; a.ldh = (int64_t)t->hist_cap * nmel; a.hist_cap = t->hist_cap;  // enables stop history
+        a.hist = t->mel_hist; a.ldh = t->hist_ld; a.hist_cap = t->hist_cap;  // enables stop history
+        const bool queue = tf || t->nq != nmel;
+        if (queue) {
+            // the next step's queue: free running it ends in the frames launch 8 just stored in the
+            // history; teacher forced it ends in teacher row t, and the stopnet reads the output apart.
+            // Launch 8 appends nothing for a finished sentence while the window keeps moving with the
+            // step word: such a sentence reads rows of an earlier call or the create-time zeros
+            // (finite either way), its GEMM row is independent of the others and nothing of it is kept.
+            a.seg[0] = Seg{t->queue0, (int)t->hist_ld, t->nq};
+            a.K = t->nq + T_DEC;
+            a.mf.win = nmel;
+            if (tf) {
+                a.seg[2] = Seg{t->mem, nmel, nmel};
+                a.nseg = 3;
+                a.W = t->W_p1t; a.K += nmel;
+            }
+        }
         MelFused& m = a.mf;
         m.nmel = 0; m.pre1 = t->pre1; m.ldp = T_PRE1;
         m.stop_hist = t->stop_hist; m.stop_ldb = t->hist_cap;
@@ -554,9 +590,9 @@ tts_status enqueue_step(tts_tacotron* t, int B, int Lmax, int max_steps, int p, 
         m.state_next = t->state + 2 * q;
         m.stop_acc = t->state + 4;
         m.max_steps = max_steps;
-        m.rule = 1;
+        m.rule = tf ? 2 : 1;
         MARK();
-        TTS_HIP(sgemm_launch(a, ROLE_T_PRE1_STOP, s));
+        TTS_HIP(sgemm_launch(a, queue ? ROLE_T_PRE1_STOP_Q : ROLE_T_PRE1_STOP, s));
     }
     MARK();
 #undef MARK
@@ -570,16 +606,31 @@ tts_status enqueue_prenet_go(tts_tacotron* t, int B, hipStream_t s) {
     a.step = t->state;
     a.out_par = -1;
     a.seg[0] = Seg{t->mem, t->nmel, t->nmel};
+    if (t->nq != t->nmel) a.seg[0] = Seg{t->queue0, (int)t->hist_ld, t->nq};  // the queue the init filled
     a.nseg = 1;
-    a.W = t->W_go; a.K = t->nmel; a.N = T_PRE1; a.bias = t->b_go; a.act = ACT_RELU;
+    a.W = t->W_go; a.K = t->nq; a.N = T_PRE1; a.bias = t->b_go; a.act = ACT_RELU;
     a.out = t->pre1; a.ldo = T_PRE1;
     TTS_HIP(sgemm_launch(a, ROLE_T_PRENET1, s));
     return TTS_OK;
 }
 
+// Decoder._init_states + Attention.init_states over the handle's buffers (tacotron_init_kernel)
+TInitArgs make_init_args(tts_tacotron* t, int B) {
+    TInitArgs ia{};
+    ia.B = B; ia.Lcap = t->Lcap; ia.nmel = t->nmel; ia.lens = t->lens;
+    ia.att_init = t->att_init; ia.dec_init = t->dec_init; ia.mem_init = t->mem_init;
+    ia.h_att = t->h_att; ia.h1 = t->h1; ia.h2 = t->h2; ia.h_pstride = (int64_t)t->Bcap * T_DEC;
+    ia.xa = t->xa; ia.mem = t->mem;
+    ia.alpha = t->alpha; ia.att_w = t->att_w; ia.att_cum = t->att_cum; ia.u = t->u; ia.win_idx = t->win_idx;
+    ia.nidx = t->nidx; ia.tail = t->tail; ia.flag1 = t->flag1; ia.count = t->count; ia.done = t->done;
+    ia.n_steps = t->n_steps; ia.state = t->state;
+    if (t->nq != t->nmel) { ia.queue = t->queue0; ia.queue_ld = t->hist_ld; ia.nq = t->nq; }
+    return ia;
+}
+
 tts_status create_weights(tts_tacotron* t, const WeightMap& wm, hipStream_t s) {
     const tts_tacotron_config& c = t->cfg;
-    const int nmel = t->nmel;
+    const int nmel = t->nmel, nq = t->nq;
     tts_status st = TTS_OK;
     // ---- encoder: embedding, prenet, CBHG(K=16, [128, 128])
     {
@@ -642,23 +693,28 @@ tts_status create_weights(tts_tacotron* t, const WeightMap& wm, hipStream_t s) {
     }
     // ---- decoder
     {
-        GET(pw0, "decoder.prenet.layers.0.linear_layer.weight", (int64_t)T_PRE1 * nmel);
+        GET(pw0, "decoder.prenet.layers.0.linear_layer.weight", (int64_t)T_PRE1 * nq);
         GET(pb0, "decoder.prenet.layers.0.linear_layer.bias", T_PRE1);
         GET(pw1, "decoder.prenet.layers.1.linear_layer.weight", T_PRE2 * T_PRE1);
         GET(pb1, "decoder.prenet.layers.1.linear_layer.bias", T_PRE2);
         GET(sw, "decoder.stopnet.linear.weight", T_DEC + nmel);
         GET(sb, "decoder.stopnet.linear.bias", 1);
-        TTS_TRY(pack_linear(t->dev, pw0, T_PRE1, nmel, &t->W_go, s));
+        TTS_TRY(pack_linear(t->dev, pw0, T_PRE1, nq, &t->W_go, s));
         TTS_TRY(pack_bias(t->dev, pb0, nullptr, T_PRE1, ROWMAP_IDENTITY, 0, &t->b_go, s));
         TTS_TRY(pack_linear(t->dev, pw1, T_PRE2, T_PRE1, &t->W_p2, s));
         TTS_TRY(pack_bias(t->dev, pb1, nullptr, T_PRE2, ROWMAP_IDENTITY, 0, &t->b_p2, s));
         float *wf = nullptr, *bf = nullptr;
-        const int K = nmel + T_DEC;
-        TTS_HIP(hipMalloc(&wf, sizeof(float) * (T_PRE1 + 1) * K));
+        const int K = nq + T_DEC;
+        TTS_HIP(hipMalloc(&wf, sizeof(float) * (T_PRE1 + 1) * (K + nmel)));
         TTS_HIP(hipMalloc(&bf, sizeof(float) * (T_PRE1 + 1)));
-        hipError_t e = fold_pre1_stop(pw0, pb0, sw, sb, nmel, wf, bf, s);
+        hipError_t e = fold_pre1_stop(pw0, pb0, sw, sb, nmel, nq, 0, wf, bf, s);
         if (e == hipSuccess) st = pack_linear(t->dev, wf, T_PRE1 + 1, K, &t->W_p1s, s);
         if (e == hipSuccess && !st) st = pack_bias(t->dev, bf, nullptr, T_PRE1 + 1, ROWMAP_IDENTITY, 0, &t->b_p1s, s);
+        // teacher-forcing form (same biases); stream order keeps wf's reuse behind the pack above.
+        // Built here, not at the first tts_tacotron_decode_teacher, because the caller's tensors need
+        // not outlive create: one more fold + pack and 257 * (nq + 256 + nmel) floats (<= 2.1 MB) per handle.
+        if (e == hipSuccess && !st) e = fold_pre1_stop(pw0, pb0, sw, sb, nmel, nq, 1, wf, bf, s);
+        if (e == hipSuccess && !st) st = pack_linear(t->dev, wf, T_PRE1 + 1, K + nmel, &t->W_p1t, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         (void)hipFree(wf);
         (void)hipFree(bf);
@@ -719,10 +775,10 @@ tts_status create_weights(tts_tacotron* t, const WeightMap& wm, hipStream_t s) {
         TTS_TRY(pack_linear(t->dev, mw, nmel, T_DEC, &t->W_mel, s));
         TTS_TRY(pack_bias(t->dev, mb, nullptr, nmel, ROWMAP_IDENTITY, 0, &t->b_mel, s));
         GET(ai, "decoder.attention_rnn_init.weight", T_DEC);
-        GET(mi, "decoder.memory_init.weight", nmel);
+        GET(mi, "decoder.memory_init.weight", nq);
         GET(di, "decoder.decoder_rnn_inits.weight", 2 * T_DEC);
         TTS_TRY(copy_weight(t->dev, &t->att_init, ai, T_DEC, s));
-        TTS_TRY(copy_weight(t->dev, &t->mem_init, mi, nmel, s));
+        TTS_TRY(copy_weight(t->dev, &t->mem_init, mi, nq, s));
         TTS_TRY(copy_weight(t->dev, &t->dec_init, di, 2 * T_DEC, s));
     }
     // ---- PostCBHG(K=8, [256, 80]) + last_linear
@@ -769,7 +825,16 @@ tts_status create_workspace(tts_tacotron* t, hipStream_t s) {
     TTS_TRY(t->dev.alloc(&t->done, Bc));
     TTS_TRY(t->dev.alloc(&t->n_steps, Bc));
     TTS_TRY(t->dev.alloc(&t->state, 8));  // {step, n_active} x 2 parities, stop_acc
-    TTS_TRY(t->dev.alloc(&t->mel_hist, (size_t)Bc * t->hist_cap * t->nmel));
+    // (layout: tts_tacotron::queue0; memory_size == r keeps the history's own stride.  The allocation
+    // always starts with one nq-float head, so that queue0 + t * nmel is a legal window for every
+    // t >= 1 of sentence 0 when memory_size == r, where teacher forcing is the only reader.)
+    t->hist_ld = (int64_t)t->hist_cap * t->nmel + (t->nq != t->nmel ? t->nq : 0);
+    TTS_TRY(t->dev.alloc(&t->queue0, (size_t)t->nq + (size_t)Bc * t->hist_ld));
+    t->mel_hist = t->queue0 + t->nq;
+    // The queue windows also cover rows no step has written (a finished sentence's, the last teacher
+    // step's): they only meet zero weights or feed discarded rows, but 0 * NaN is NaN, so the
+    // buffer never holds anything but zeros, frames and teacher rows.
+    TTS_HIP(hipMemsetAsync(t->queue0, 0, sizeof(float) * ((size_t)t->nq + (size_t)Bc * t->hist_ld), s));
     TTS_TRY(t->dev.alloc(&t->stop_hist, (size_t)Bc * t->hist_cap));
     TTS_TRY(t->dev.alloc(&t->align_hist, (size_t)Bc * t->hist_cap * Lc));
     TTS_TRY(t->dev.alloc(&t->ids, (size_t)Bc * std::max(Lc, 1)));
@@ -786,14 +851,15 @@ tts_status create_workspace(tts_tacotron* t, hipStream_t s) {
 }
 
 // The resident decoder serves the attention configuration of config_tacotron_gst.json (sigmoid norm,
-// forward attention without the eval mask, no transition agent / location / windowing) on a GPU
+// forward attention without the eval mask, no transition agent / location / windowing) with a memory
+// queue of at most TR_NMEL_MAX = 512 values (every r <= 5 at memory_size 5, r = memory_size = 6) on a GPU
 // with >= 256 compute units; TTS_RESIDENT=0 at create disables it.  Its weights are plain copies of
 // the reference tensors (the kernel picks its rows at launch).
 tts_status create_resident(tts_tacotron* t, const WeightMap& wm, hipStream_t s) {
     const tts_tacotron_config& c = t->cfg;
     int dev = 0, ncu = 0, rate_khz = 0;
     if (!(c.attn_norm == 1 && c.forward_attn && !c.trans_agent && !c.forward_attn_mask && !c.location_attn &&
-          !c.windowing && t->nmel <= TR_NMEL_MAX && c.max_steps <= 1000) ||
+          !c.windowing && t->nq <= TR_NMEL_MAX && c.max_steps <= 1000) ||
         env_is("TTS_RESIDENT", '0') || hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < TR_CUS ||
         hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || rate_khz <= 0 ||
@@ -824,7 +890,7 @@ tts_status create_resident(tts_tacotron* t, const WeightMap& wm, hipStream_t s) 
     CPY(a.b_proj, "decoder.project_to_decoder_in.bias", T_DEC);
     CPY(a.w_mel, "decoder.proj_to_mel.weight", (int64_t)nmel * T_DEC);
     CPY(a.b_mel, "decoder.proj_to_mel.bias", nmel);
-    CPY(a.w_pre1, "decoder.prenet.layers.0.linear_layer.weight", (int64_t)T_PRE1 * nmel);
+    CPY(a.w_pre1, "decoder.prenet.layers.0.linear_layer.weight", (int64_t)T_PRE1 * t->nq);
     CPY(a.b_pre1, "decoder.prenet.layers.0.linear_layer.bias", T_PRE1);
     CPY(a.w_pre2, "decoder.prenet.layers.1.linear_layer.weight", T_PRE2 * T_PRE1);
     CPY(a.b_pre2, "decoder.prenet.layers.1.linear_layer.bias", T_PRE2);
@@ -834,6 +900,9 @@ tts_status create_resident(tts_tacotron* t, const WeightMap& wm, hipStream_t s) 
 #undef CPY
     a.v = t->v;
     a.v_b = t->v_b;
+    a.nq = t->nq;
+    a.mem_init = t->mem_init;
+    a.hist_ld = t->hist_ld;
     if ((st = t->dev.alloc(&t->tr_gran, tres_granules() + 2))) return st;
     TTS_HIP(hipMemsetAsync(t->tr_gran, 0, sizeof(unsigned long long) * (tres_granules() + 2), s));
     t->res_ticks = (long long)rate_khz * 50;  // 50 ms per hand-off wait
@@ -869,7 +938,10 @@ tts_status tts_tacotron_create(const tts_tacotron_config* cfg, const tts_tensor*
     TTS_CHECK(cfg && out && (tensors || n_tensors == 0), TTS_ERR_INVALID, "null argument");
     TTS_CHECK(cfg->r >= 1 && cfg->r <= 8, TTS_ERR_INVALID, "r must be in [1, 8]");
     const int ms = cfg->memory_size > 0 ? cfg->memory_size : cfg->r;
-    TTS_CHECK(ms == cfg->r, TTS_ERR_UNSUPPORTED, "memory_size must equal r (the configs' memory queue)");
+    TTS_CHECK(ms >= cfg->r, TTS_ERR_INVALID,
+              "memory_size must be >= r: the reference decoder cannot run a shorter queue (its first queue update "
+              "leaves 80 * r values for a prenet of 80 * memory_size: mat1 and mat2 shapes cannot be multiplied)");
+    TTS_CHECK(ms <= TTS_TACOTRON_MEMORY_SIZE_MAX, TTS_ERR_UNSUPPORTED, "memory_size exceeds TTS_TACOTRON_MEMORY_SIZE_MAX");
     TTS_CHECK(cfg->max_batch >= 1 && cfg->max_batch <= 64, TTS_ERR_UNSUPPORTED, "max_batch must be in [1, 64]");
     TTS_CHECK(cfg->max_len >= 1 && cfg->max_len <= (cfg->location_attn ? 512 : 1024), TTS_ERR_UNSUPPORTED,
               "max_len must be in [1, 1024] (512 with location attention)");
@@ -880,6 +952,8 @@ tts_status tts_tacotron_create(const tts_tacotron_config* cfg, const tts_tensor*
     t->cfg = *cfg;
     t->cfg.memory_size = ms;
     t->nmel = 80 * cfg->r;
+    t->nq = 80 * ms;
+    static_assert(NQ_MAX + T_DEC + 80 * 8 <= 2560, "the batch-1 GEMM holds K <= 2560 in one round of loads");
     hipStream_t s = static_cast<hipStream_t>(stream);
     auto fail = [&](tts_status code) {
         tts_tacotron_destroy(t);
@@ -1002,14 +1076,7 @@ tts_status tts_tacotron_decode(tts_tacotron* t, const float* enc, const int32_t*
                              B, hipMemcpyDeviceToDevice, s));
     TTS_HIP(hipMemcpyAsync(t->lens, lens, sizeof(int) * B, hipMemcpyHostToDevice, s));
     TTS_HIP(launch_project_inputs(t->denc, t->W_in, B, Lmax, t->Lcap, t->Pt, s, T_DEC));
-    TInitArgs ia{};
-    ia.B = B; ia.Lcap = t->Lcap; ia.nmel = t->nmel; ia.lens = t->lens;
-    ia.att_init = t->att_init; ia.dec_init = t->dec_init; ia.mem_init = t->mem_init;
-    ia.h_att = t->h_att; ia.h1 = t->h1; ia.h2 = t->h2; ia.h_pstride = (int64_t)t->Bcap * T_DEC;
-    ia.xa = t->xa; ia.mem = t->mem;
-    ia.alpha = t->alpha; ia.att_w = t->att_w; ia.att_cum = t->att_cum; ia.u = t->u; ia.win_idx = t->win_idx;
-    ia.nidx = t->nidx; ia.tail = t->tail; ia.flag1 = t->flag1; ia.count = t->count; ia.done = t->done;
-    ia.n_steps = t->n_steps; ia.state = t->state;
+    const TInitArgs ia = make_init_args(t, B);
     TTS_HIP(launch_tacotron_init(ia, s));
     { tts_status st = enqueue_prenet_go(t, B, s); if (st) return st; }
     int run = 0;
@@ -1101,7 +1168,7 @@ tts_status tts_tacotron_decode(tts_tacotron* t, const float* enc, const int32_t*
     int nmax = 0;
     for (int b = 0; b < B; ++b) nmax = std::max(nmax, (int)n_steps[b]);
     const size_t nm = t->nmel;
-    TTS_HIP(hipMemcpy2DAsync(mel, (size_t)steps_cap * nm * 4, t->mel_hist, (size_t)t->hist_cap * nm * 4,
+    TTS_HIP(hipMemcpy2DAsync(mel, (size_t)steps_cap * nm * 4, t->mel_hist, (size_t)t->hist_ld * 4,
                              (size_t)nmax * nm * 4, B, hipMemcpyDeviceToDevice, s));
     TTS_HIP(hipMemcpy2DAsync(stop, (size_t)steps_cap * 4, t->stop_hist, (size_t)t->hist_cap * 4, (size_t)nmax * 4, B,
                              hipMemcpyDeviceToDevice, s));
@@ -1118,6 +1185,62 @@ tts_status tts_tacotron_decode(tts_tacotron* t, const float* enc, const int32_t*
     t->last_max_steps = max_steps;
     t->last_first = first;
     t->last_init = ia;
+    return TTS_OK;
+}
+
+tts_status tts_tacotron_decode_teacher(tts_tacotron* t, const float* enc, const int32_t* lens, int B, int Lmax,
+                                       const float* memories, int64_t mem_ldb, int steps, float* mel, float* stop,
+                                       float* align, void* stream) {
+    TTS_CHECK(t && enc && lens && memories && mel && stop, TTS_ERR_INVALID, "null argument");
+    TTS_CHECK(B >= 1 && B <= t->Bcap, TTS_ERR_INVALID, "batch exceeds decoder capacity");
+    TTS_CHECK(Lmax >= 1 && Lmax <= t->Lcap, TTS_ERR_INVALID, "Lmax exceeds decoder capacity");
+    TTS_CHECK(steps >= 1 && steps <= t->hist_cap, TTS_ERR_INVALID, "teacher steps exceed the decoder's history capacity");
+    TTS_CHECK(mem_ldb >= (int64_t)(steps - 1) * t->nmel, TTS_ERR_INVALID, "teacher memory rows too short");
+    TTS_CHECK(!t->cfg.forward_attn_mask || Lmax >= 2, TTS_ERR_INVALID, "forward_attn_mask needs L >= 2");
+    for (int b = 0; b < B; ++b) {
+        TTS_CHECK(lens[b] >= 1 && lens[b] <= Lmax, TTS_ERR_INVALID, "encoder length out of range [1, Lmax]");
+        TTS_CHECK(!t->cfg.forward_attn_mask || lens[b] >= 2, TTS_ERR_INVALID, "forward_attn_mask needs L >= 2");
+    }
+    hipStream_t cs = static_cast<hipStream_t>(stream);
+    hipStream_t s = t->stream;
+    const size_t nm = t->nmel;
+    TTS_HIP(hipEventRecord(t->ev_in, cs));
+    TTS_HIP(hipStreamWaitEvent(s, t->ev_in, 0));
+    TTS_HIP(hipMemcpy2DAsync(t->denc, (size_t)t->Lcap * T_DEC * 4, enc, (size_t)Lmax * T_DEC * 4, (size_t)Lmax * T_DEC * 4,
+                             B, hipMemcpyDeviceToDevice, s));
+    TTS_HIP(hipMemcpyAsync(t->lens, lens, sizeof(int) * B, hipMemcpyHostToDevice, s));
+    TTS_HIP(launch_project_inputs(t->denc, t->W_in, B, Lmax, t->Lcap, t->Pt, s, T_DEC));
+    // the teacher frames take the history's place: step t + 1's queue then ends in teacher row t.
+    // The last step's launch 9 still reads a window ending in row steps - 1, which no step consumes
+    // (only its zero-weighted stopnet columns and a prenet row nobody reads): zeros, so that the last
+    // stop logit does not depend on what an earlier call left there.
+    if (steps > 1)
+        TTS_HIP(hipMemcpy2DAsync(t->mel_hist, (size_t)t->hist_ld * 4, memories, (size_t)mem_ldb * 4,
+                                 (size_t)(steps - 1) * nm * 4, B, hipMemcpyDeviceToDevice, s));
+    TTS_HIP(hipMemset2DAsync(t->mel_hist + (size_t)(steps - 1) * nm, (size_t)t->hist_ld * 4, 0, nm * 4, B, s));
+    const TInitArgs ia = make_init_args(t, B);
+    TTS_HIP(launch_tacotron_init(ia, s));
+    { tts_status st = enqueue_prenet_go(t, B, s); if (st) return st; }
+    t->last_resident = 0;
+    const TeacherOut tf{mel, steps};
+    TTS_HIP(hipEventRecord(t->ev_t0, s));
+    for (int k = 0; k < steps; ++k) {
+        tts_status st = enqueue_step(t, B, Lmax, steps, k & 1, s, nullptr, &tf);
+        if (st) return st;
+    }
+    TTS_HIP(hipEventRecord(t->ev_t1, s));
+    TTS_HIP(hipMemcpy2DAsync(stop, (size_t)steps * 4, t->stop_hist, (size_t)t->hist_cap * 4, (size_t)steps * 4, B,
+                             hipMemcpyDeviceToDevice, s));
+    if (align)
+        TTS_HIP(hipMemcpy2DAsync(align, (size_t)steps * Lmax * 4, t->align_hist, (size_t)t->hist_cap * Lmax * 4,
+                                 (size_t)steps * Lmax * 4, B, hipMemcpyDeviceToDevice, s));
+    TTS_HIP(hipEventRecord(t->ev_out, s));
+    TTS_HIP(hipStreamWaitEvent(cs, t->ev_out, 0));
+    TTS_HIP(hipStreamSynchronize(s));
+    TTS_HIP(hipEventElapsedTime(&t->last_ms, t->ev_t0, t->ev_t1));
+    t->last_steps = steps;
+    // (the profiling entry points re-run the last free-running decode: this call leaves none)
+    t->last_B = 0;
     return TTS_OK;
 }
 

@@ -99,6 +99,8 @@ __global__ void tacotron_init_kernel(const TInitArgs a) {
         a.xa[(int64_t)b * T_XA + T_PRE2 + k] = 0.f;  // current_context_vec = 0 (:352)
     }
     for (int k = threadIdx.x; k < a.nmel; k += blockDim.x) a.mem[(int64_t)b * a.nmel + k] = a.mem_init[k];  // :343
+    if (a.queue)  // memory queue wider than a frame group: memory_init fills it (:310, 343)
+        for (int k = threadIdx.x; k < a.nq; k += blockDim.x) a.queue[(int64_t)b * a.queue_ld + k] = a.mem_init[k];
     for (int j = threadIdx.x; j < a.Lcap; j += blockDim.x) {  // init_forward_attn: [1, 1e-7, ...]
         const int64_t o = (int64_t)b * a.Lcap + j;
         a.alpha[o] = j == 0 ? 1.f : (j < L ? 1e-7f : 0.f);
@@ -236,26 +238,33 @@ hipError_t launch_gather_rows(const float* table, const int* ids, int width, flo
 }
 
 __global__ void fold_pre1_stop_kernel(const float* W1, const float* b1, const float* ws, const float* bs, int nmel,
-                                      float* Wf, float* bf) {
-    const int K = nmel + T_DEC;
+                                      int nq, int split_out, float* Wf, float* bf) {
+    const int K = nq + T_DEC + (split_out ? nmel : 0);
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)(T_PRE1 + 1) * (K + 1)) return;
     const int n = i / (K + 1), k = i % (K + 1);
     float v;
-    if (n < T_PRE1)
-        v = k < K ? (k < nmel ? W1[(int64_t)n * nmel + k] : 0.f) : b1[n];
-    else
-        v = k < K ? (k < nmel ? ws[T_DEC + k] : ws[k - nmel]) : bs[0];
+    if (n < T_PRE1) {
+        v = k < K ? (k < nq ? W1[(int64_t)n * nq + k] : 0.f) : b1[n];
+    } else if (k == K) {
+        v = bs[0];
+    } else if (split_out) {
+        v = k < nq ? 0.f : ws[k - nq];  // [decoder out | mel out] is the stopnet's own order
+    } else {
+        // the output is the queue's last nmel values
+        v = k < nq - nmel ? 0.f : (k < nq ? ws[T_DEC + k - (nq - nmel)] : ws[k - nq]);
+    }
     if (k < K)
         Wf[(int64_t)n * K + k] = v;
     else
         bf[n] = v;
 }
 
-hipError_t fold_pre1_stop(const float* W1, const float* b1, const float* ws, const float* bs, int nmel, float* Wf,
-                          float* bf, hipStream_t s) {
-    const int64_t total = (int64_t)(T_PRE1 + 1) * (nmel + T_DEC + 1);
-    hipLaunchKernelGGL(fold_pre1_stop_kernel, dim3((total + 255) / 256), dim3(256), 0, s, W1, b1, ws, bs, nmel, Wf, bf);
+hipError_t fold_pre1_stop(const float* W1, const float* b1, const float* ws, const float* bs, int nmel, int nq,
+                          int split_out, float* Wf, float* bf, hipStream_t s) {
+    const int64_t total = (int64_t)(T_PRE1 + 1) * (nq + T_DEC + (split_out ? nmel : 0) + 1);
+    hipLaunchKernelGGL(fold_pre1_stop_kernel, dim3((total + 255) / 256), dim3(256), 0, s, W1, b1, ws, bs, nmel, nq,
+                       split_out, Wf, bf);
     return hipGetLastError();
 }
 

@@ -188,6 +188,11 @@ __device__ __forceinline__ float to_lanes(const float (&p)[TR_SPX], int lane) {
     return __shfl(tot, 16 * (lane & 3), 64);
 }
 
+// QUEUE: memory_size > r (layers/tacotron.py:396-404).  The LDS `mel` rows are then each sentence's
+// memory queue of nq = 80 * memory_size values: initialised from memory_init, shifted by nmel and
+// extended with the step's output after the mel gather; prenet layer 1 and the stopnet read it whole
+// (the stopnet's mel weights sit at the output's offset nq - nmel).  memory_size == r keeps its code.
+template <bool QUEUE>
 __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const TResArgs a) {
     const int c = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -244,6 +249,8 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
     const int ns = min(TR_SPX, a.B - b0);                // its sentences
     if (r >= TR_RANKS || ns <= 0) return;                // idle CU / group
     const int nmel = a.nmel;
+    const int nq = QUEUE ? a.nq : nmel;  // prenet layer-1 input width
+    const int qo = nq - nmel;            // offset of a step's output in the queue
     // ---- weights into registers (reference layouts): lane l holds k = 4l + i of every 256-wide
     // segment (one ds_read_b128 of the input per segment), k = 2l + i of the 128-wide prenet part
     const int U = 8 * r + wave;  // attention-GRU / decoder-GRU unit, proj row, prenet-L1 row
@@ -288,7 +295,7 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const int k = 8 * lane + i;
-        w1[(i >> 2) * 256 + lane * 4 + (i & 3)] = k < nmel ? a.w_pre1[(int64_t)U * nmel + k] : 0.f;
+        w1[(i >> 2) * 256 + lane * 4 + (i & 3)] = k < nq ? a.w_pre1[(int64_t)U * nq + k] : 0.f;
     }
     const int r2 = 4 * r + (wave & 3);  // prenet-L2 row (waves 0-3) / query row (waves 4-7)
     float w2q[4];
@@ -338,9 +345,10 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
     }
     if (tid < ADIM) sm[L_V + tid] = a.v[tid];
     const float vb = a.v_b[0];
-    // stopnet row (rank 0): [decoder out 256 | mel nmel]
+    // stopnet row (rank 0): [decoder out 256 | mel nmel], the mel part at the output's queue offset
     if (r == 0)
-        for (int k = tid; k < TD + TR_NMEL_MAX; k += TR_THREADS) sm[L_STOP + k] = k < TD + nmel ? a.w_stop[k] : 0.f;
+        for (int k = tid; k < TD + TR_NMEL_MAX; k += TR_THREADS)
+            sm[L_STOP + k] = k < TD ? a.w_stop[k] : (k >= TD + qo && k < TD + nq ? a.w_stop[k - qo] : 0.f);
     const float bstop = a.b_stop[0];
     // ---- initial state (slot 1 of h, context 0, prenet L1 of the go frame)
     for (int i = tid; i < TR_SPX * TD; i += TR_THREADS) {
@@ -352,7 +360,8 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
         sm[L_PRE1 + i] = on ? a.pre1[(int64_t)b * T_PRE1 + k] : 0.f;
     }
     for (int i = tid; i < TR_SPX * TXA; i += TR_THREADS) sm[L_XA + i] = 0.f;
-    for (int i = tid; i < TR_SPX * TR_NMEL_MAX; i += TR_THREADS) sm[L_MEL + i] = 0.f;
+    for (int i = tid; i < TR_SPX * TR_NMEL_MAX; i += TR_THREADS)  // Decoder._init_states: memory_init (:343)
+        sm[L_MEL + i] = QUEUE && i / TR_NMEL_MAX < ns && i % TR_NMEL_MAX < nq ? a.mem_init[i % TR_NMEL_MAX] : 0.f;
     int* dn = ctl + 4;  // done flags of the group's sentences (as of this step's start)
     if (tid < TR_SPX) dn[tid] = tid < ns ? 0 : 1;
     int Ls[TR_SPX];
@@ -704,20 +713,48 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
                 publish(G + G_MEL + lane * TR_NMEL_MAX + m0, E + P_MEL, o0);
                 publish(G + G_MEL + lane * TR_NMEL_MAX + m1, E + P_MEL, o1);
                 if (t < a.hist_cap) {
-                    if (m0 < nmel) a.mel_hist[((int64_t)b * a.hist_cap + t) * nmel + m0] = o0;
-                    if (m1 < nmel) a.mel_hist[((int64_t)b * a.hist_cap + t) * nmel + m1] = o1;
+                    float* row = a.mel_hist + (QUEUE ? b * a.hist_ld : (int64_t)b * a.hist_cap * nmel) + (int64_t)t * nmel;
+                    if (m0 < nmel) row[m0] = o0;
+                    if (m1 < nmel) row[m1] = o1;
                 }
             }
         }
         MARK(15);
-        if (gon) {
-            float v4[4];
-            const bool ok = sweep<4>(G + G_MEL, E + P_MEL, v4, [&](int i) {
-                return gs * TR_NMEL_MAX + gf * 256 + ln + 64 * i;
-            }, tmo, fsl);
+        if (!QUEUE) {
+            if (gon) {
+                float v4[4];
+                const bool ok = sweep<4>(G + G_MEL, E + P_MEL, v4, [&](int i) {
+                    return gs * TR_NMEL_MAX + gf * 256 + ln + 64 * i;
+                }, tmo, fsl);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) mel[gs * TR_NMEL_MAX + gf * 256 + lane + 64 * i] = v4[i];
-            if (!ok && lane == 0) { ctl[0] = 1; fail(a.status, 12); }
+                for (int i = 0; i < 4; ++i) mel[gs * TR_NMEL_MAX + gf * 256 + lane + 64 * i] = v4[i];
+                if (!ok && lane == 0) { ctl[0] = 1; fail(a.status, 12); }
+            }
+        } else {
+            // _update_memory_queue (:396-404): queue = cat(queue[nmel:], output).  The ranges overlap
+            // across threads: every thread reads the values it moves, barrier, then writes.
+            float v4[4], keep[4];
+            float* qs = mel + gs * TR_NMEL_MAX;
+            if (gon) {
+                const bool ok = sweep<4>(G + G_MEL, E + P_MEL, v4, [&](int i) {
+                    return gs * TR_NMEL_MAX + gf * 256 + ln + 64 * i;
+                }, tmo, fsl);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int k = gf * 256 + lane + 64 * i;
+                    keep[i] = k < qo ? qs[k + nmel] : 0.f;  // k + nmel < nq <= TR_NMEL_MAX
+                }
+                if (!ok && lane == 0) { ctl[0] = 1; fail(a.status, 12); }
+            }
+            __syncthreads();
+            if (gon) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int k = gf * 256 + lane + 64 * i;
+                    if (k < qo) qs[k] = keep[i];
+                    if (k < nmel) qs[qo + k] = v4[i];  // qo + k < nq
+                }
+            }
         }
         __syncthreads();
         if (ctl[0]) return;
@@ -750,7 +787,7 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
                 publish(G + G_PRE1 + TR_SPX * T_PRE1 + s, E + P_PRE1, nd ? 0.f : 1.f);
             }
         }
-        // prenet L1 of step t+1, row U (memory = this output, memory_size == r: :396-404)
+        // prenet L1 of step t+1, row U (memory = this output, or the queue it now ends: :396-404)
         {
             float p[TR_SPX];
             const float4 wa = ld4(w1 + 4 * lane), wb = ld4(w1 + 256 + 4 * lane);
@@ -777,7 +814,10 @@ size_t tres_granules() { return (size_t)G_TOTAL + 2; }
 size_t tres_smem_bytes() { return (size_t)L_TOTAL * sizeof(float); }
 
 hipError_t tres_prepare() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&tacotron_resident_kernel),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tacotron_resident_kernel<false>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)tres_smem_bytes());
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&tacotron_resident_kernel<true>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)tres_smem_bytes());
 }
 
@@ -785,10 +825,14 @@ hipError_t launch_tacotron_resident(const TResArgs& a, hipStream_t s, bool* laun
     *launched = false;
     if (a.B < 1 || a.B > TR_SPX * TR_GROUPS || a.nmel > TR_NMEL_MAX || a.Lalign > TR_LMAX || a.max_steps > 1000)
         return hipErrorInvalidValue;
+    const bool queue = a.nq != a.nmel;
+    if (queue && (a.nq < a.nmel || a.nq > TR_NMEL_MAX || !a.mem_init || a.hist_ld < (int64_t)a.hist_cap * a.nmel))
+        return hipErrorInvalidValue;
     TResArgs arg = a;
     void* args[] = {&arg};
-    return launch_persistent(reinterpret_cast<const void*>(&tacotron_resident_kernel), dim3(TR_CUS), dim3(TR_THREADS),
-                             args, tres_smem_bytes(), s, launched);
+    const void* fn = queue ? reinterpret_cast<const void*>(&tacotron_resident_kernel<true>)
+                           : reinterpret_cast<const void*>(&tacotron_resident_kernel<false>);
+    return launch_persistent(fn, dim3(TR_CUS), dim3(TR_THREADS), args, tres_smem_bytes(), s, launched);
 }
 
 }  // namespace tts

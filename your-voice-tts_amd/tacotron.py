@@ -3,7 +3,10 @@
 
 Same constructor arguments, ``state_dict`` keys and shapes (reference checkpoints load with
 ``load_state_dict(cp['model'])``), same ``inference`` return tuple
-``(mel_outputs [B,T*r,80], linear_outputs [B,T*r,1025], alignments [B,T,L], stop_tokens [B,T])``.
+``(mel_outputs [B,T*r,80], linear_outputs [B,T*r,1025], alignments [B,T,L], stop_tokens [B,T])``,
+and the teacher-forced ``forward`` / ``decoder_forward`` in eval mode.  ``memory_size >= r`` frames
+of decoder memory queue (layers/tacotron.py:279-287, 396-404) are served; a shorter queue raises
+``ValueError`` (the reference cannot run one either).
 
 Everything runs in libtts_hip (``tts_tacotron_*``, tacotron_api.hip): embedding + Prenet + CBHG
 encoder, speaker embedding, the GST reference encoder and style-token attention, the
@@ -51,9 +54,12 @@ class TacotronGST:
         self.r = r
         self.mel_dim = mel_dim
         self.linear_dim = linear_dim
-        self.memory_size = memory_size if memory_size > 0 else r
-        if self.memory_size != r:
-            raise NotImplementedError("memory_size != r is not on the MI355X path (every config uses 5 = r)")
+        self.memory_size = memory_size if memory_size > 0 else r  # layers/tacotron.py:279
+        if self.memory_size < r:
+            # the reference builds such a decoder, but its first queue update leaves 80 * r values for a
+            # prenet of 80 * memory_size ("mat1 and mat2 shapes cannot be multiplied")
+            raise ValueError(f"memory_size={self.memory_size} < r={r}: the decoder memory queue must hold at "
+                             f"least one step's frames")
         self.num_chars = num_chars
         self.num_speakers = num_speakers
         self.flags = dict(r=r, attn_norm=attn_norm, forward_attn=bool(forward_attn), trans_agent=bool(trans_agent),
@@ -131,15 +137,22 @@ class TacotronGST:
             pass
 
     # ------------------------------------------------------------------ native handle
-    def _handle(self, Lmax, B):
+    def _handle(self, Lmax, B, need_steps=0):
+        """need_steps: steps the handle's history must hold (max_decoder_steps + 1 always fit); a handle
+        with more room is kept.  0 (the free-running decoder): the handle's step capacity is
+        max_decoder_steps itself."""
         lib = _native.lib()
         if self.device.type != "cuda":
             self.cuda()
-        max_steps = int(self.decoder.max_decoder_steps)
+        max_steps = max(int(self.decoder.max_decoder_steps), need_steps - 1)
         key = (max_steps, max(self.max_len, Lmax), max(self.max_batch, B))
-        if self._native is not None and (self._native[1][0] != max_steps or self._native[1][1] < Lmax
-                                         or self._native[1][2] < B):
-            self._drop_native()
+        if self._native is not None:
+            have = self._native[1]
+            # the encoder, the postnet and teacher forcing only need the history to be long enough, so a
+            # forward() over a long teacher does not re-create the handle between its stages
+            steps_ok = have[0] == max_steps or (need_steps and have[0] >= max_steps)
+            if not steps_ok or have[1] < Lmax or have[2] < B:
+                self._drop_native()
         if self._native is None:
             f = self.flags
             cfg = _native.TacotronConfig(
@@ -173,7 +186,7 @@ class TacotronGST:
         """embedding -> Encoder -> + speaker embedding -> + GST(style_mel) (models/tacotrongst.py:65-73)
         for a padded batch; every sentence encoded at its own length, rows past it zero."""
         B, Lmax = ids.shape
-        lib, h = self._handle(Lmax, B)
+        lib, h = self._handle(Lmax, B, need_steps=1)
         ids32 = ids.to(self.device, dtype=torch.int32).contiguous()
         out = torch.empty(B, Lmax, 256, device=self.device)
         sid = self._per_sentence(speaker_ids, B) if self.num_speakers > 1 else None
@@ -259,7 +272,7 @@ class TacotronGST:
     @torch.no_grad()
     def postnet(self, mel, frames):
         """PostCBHG + last_linear + sigmoid (models/tacotrongst.py:77-78) on [B, T, 80] frames."""
-        lib, h = self._handle(1, mel.shape[0])
+        lib, h = self._handle(1, mel.shape[0], need_steps=1)
         mel = mel.float().contiguous()
         B, T = mel.shape[0], mel.shape[1]
         lin = torch.empty(B, T, self.linear_dim, device=self.device)
@@ -277,6 +290,76 @@ class TacotronGST:
         out = self.inference_batch([row for row in characters.cpu().numpy()], speaker_ids=speaker_ids,
                                    style_mel=style_mel)
         return out["mel"], out["linear"], out["align"], out["stop"]
+
+    # ------------------------------------------------------------------ teacher forcing
+    @torch.no_grad()
+    def decoder_forward(self, inputs, memories, mask=None):
+        """Decoder.forward(inputs, memory, mask) (layers/tacotron.py:406-437), eval mode, teacher
+        forcing: inputs [B, L, 256] encoder outputs, memories [B, T, 80] teacher mels, mask [B, L]
+        bool (True = valid position) or a list of encoder lengths (None = every sentence spans L).
+        Step t decodes from memory_init, then from the memory queue updated with teacher frame group
+        t-1; T/r steps, no stop rule.  Returns (mel [B, T/r, 80*r], alignments [B, T/r, L], stop
+        logits [B, T/r]) like the reference; each sentence is decoded at its own length."""
+        _native.lib()
+        if self.device.type != "cuda":
+            self.cuda()
+        inputs = torch.as_tensor(inputs).to(self.device).float().contiguous()
+        B, L = inputs.shape[0], inputs.shape[1]
+        if mask is None:
+            lens = [L] * B
+        else:
+            m = torch.as_tensor(mask)
+            lens = [int(x) for x in (m.reshape(B, -1).sum(1) if m.dtype == torch.bool else m.reshape(-1))]
+        if len(lens) != B or min(lens) < 1 or max(lens) > L:
+            raise ValueError(f"encoder lengths {lens} do not fit inputs of shape {tuple(inputs.shape)}")
+        if self.flags["forward_attn_mask"] and min(lens) < 2:
+            raise ValueError("encoder length must be >= 2 with forward_attn_mask")
+        r = self.r
+        memories = torch.as_tensor(memories).to(self.device).float().contiguous()
+        if memories.dim() != 3 or memories.shape[0] != B or memories.shape[2] != 80 or memories.shape[1] % r \
+                or memories.shape[1] < r:
+            raise ValueError(f"memories must be [B, T, 80] with T a positive multiple of r={r}")
+        T = memories.shape[1]
+        steps = T // r
+        lib, h = self._handle(L, B, need_steps=steps)
+        mel = torch.empty(B, steps, 80 * r, device=self.device)
+        stop = torch.empty(B, steps, device=self.device)
+        align = torch.empty(B, steps, L, device=self.device)
+        _native.check(lib.tts_tacotron_decode_teacher(
+            h, ctypes.c_void_p(inputs.data_ptr()), _native.i32_array(lens), B, L,
+            ctypes.c_void_p(memories.data_ptr()), T * 80, steps, ctypes.c_void_p(mel.data_ptr()),
+            ctypes.c_void_p(stop.data_ptr()), ctypes.c_void_p(align.data_ptr()), _native.stream_handle()),
+            "tts_tacotron_decode_teacher")
+        ms, ns = ctypes.c_float(), ctypes.c_int()
+        lib.tts_tacotron_last_timing(h, ctypes.byref(ms), ctypes.byref(ns))
+        res = ctypes.c_int()
+        lib.tts_tacotron_last_path(h, ctypes.byref(res))
+        self.last_timing = dict(decoder_loop_ms=ms.value, decoder_steps_run=ns.value, resident=bool(res.value))
+        return mel, align, stop
+
+    def _forward(self, characters, text_lengths, mel_specs, speaker_ids, style):
+        if mel_specs is None:
+            raise ValueError(f"{type(self).__name__}.forward needs mel_specs (teacher forcing)")
+        characters = torch.as_tensor(characters)
+        lens = [int(x) for x in torch.as_tensor(text_lengths).reshape(-1)]
+        B, Lmax = characters.shape[0], max(lens)
+        if self.device.type != "cuda":
+            self.cuda()
+        mel_specs = torch.as_tensor(mel_specs).to(self.device).float()
+        self._handle(Lmax, B, need_steps=mel_specs.shape[1] // self.r)  # one handle for every stage below
+        enc = self.encode(characters[:, :Lmax].to(self.device), lens, speaker_ids, mel_specs if style else None)
+        mel, align, stop = self.decoder_forward(enc, mel_specs, lens)
+        mel = mel.view(B, -1, self.mel_dim)
+        return mel, self.postnet(mel, [mel.shape[1]] * B), align, stop
+
+    @torch.no_grad()
+    def forward(self, characters, text_lengths, mel_specs, speaker_ids=None):
+        """TacotronGST.forward (models/tacotrongst.py:47-62) in eval mode: embedding + encoder at each
+        sentence's length, + speaker embedding, + GST(mel_specs), teacher-forced decoder on mel_specs
+        [B, T, 80], PostCBHG + last_linear.  Returns (mel [B, T, 80], linear [B, T, 1025], alignments
+        [B, T/r, L], stop logits [B, T/r]).  The reference's own forward cannot run on torch >= 1.2
+        (`1 - mask` on a bool mask, common_layers.py:234); this is its intended result."""
+        return self._forward(characters, text_lengths, mel_specs, speaker_ids, style=True)
 
     def profile_step_kernels(self, reps=20):
         """Mean duration (ms) of each decoder-step kernel for the batch of the last inference call."""
@@ -313,6 +396,12 @@ class Tacotron(TacotronGST):
         super().__init__(num_chars, num_speakers, r, linear_dim, mel_dim, memory_size, attn_win, attn_norm,
                          prenet_type, prenet_dropout, forward_attn, trans_agent, forward_attn_mask, location_attn,
                          separate_stopnet, **kw)
+
+    @torch.no_grad()
+    def forward(self, characters, text_lengths, mel_specs, speaker_ids=None):
+        """Tacotron.forward (models/tacotron.py:45-57) in eval mode: TacotronGST.forward without the
+        style embedding."""
+        return self._forward(characters, text_lengths, mel_specs, speaker_ids, style=False)
 
     @torch.no_grad()
     def inference(self, characters, speaker_ids=None):

@@ -202,7 +202,7 @@ def tacotron_gst_spec(num_chars: int = 130, num_speakers: int = 0, r: int = 5, m
         add("gst.style_token_layer.attention.W_query.weight", (256, 128), _default_linear(128))
         add("gst.style_token_layer.attention.W_key.weight", (256, 64), _default_linear(64))
         add("gst.style_token_layer.attention.W_value.weight", (256, 64), _default_linear(64))
-    mem = 80 * memory_size
+    mem = 80 * (memory_size if memory_size > 0 else r)  # layers/tacotron.py:279
     prenet("decoder.prenet", mem, [256, 128], prenet_bn)  # prenet_type (layers/tacotron.py:283-287)
     hb = 1.0 / math.sqrt(256)
     add("decoder.attention_rnn.weight_ih", (768, 384), ("uniform", hb))
