@@ -108,6 +108,7 @@ struct tts_decoder {
     bool rbatch = false;
     int rb_gen = 0;
     float4 *rb_wa = nullptr, *rb_wd = nullptr;
+    float* rb_loc = nullptr;                // location weights in the batch kernel's packing (general form)
     long long* rb_prof = nullptr;           // TTS_RB_PROF=1 phase clocks
     unsigned long long* rb_gran = nullptr;  // resident_batch_granules() slots, then int status[4]
     unsigned rb_salt = 0;
@@ -428,8 +429,8 @@ void choose_resident(tts_decoder* d) {
     }
 }
 
-// The resident decoders' weight layouts: batch 1 (resident.h) and, for small batches of the
-// attention configurations it covers, the batched form with both LSTMs' rows in registers
+// The resident decoders' weight layouts: batch 1 (resident.h) and, for small batches of every
+// attention configuration, the batched form with both LSTMs' rows in registers
 // (TTS_RESIDENT_BATCH=0 keeps those multi-launch).  wf / bf: the folded mel matrix and bias.
 tts_status pack_resident(tts_decoder* d, const SrcWeights& w, const float* wf, const float* bf, int nfused,
                          hipStream_t s) {
@@ -454,6 +455,10 @@ tts_status pack_resident(tts_decoder* d, const SrcWeights& w, const float* wf, c
                nfused};
     TTS_HIP(resident_pack(src, d->rw, s));
     const int gen = gen_bits(d->cfg);
+    // location features / windowing / transition agent run the general instantiations, which need
+    // the general batch-1 form's packed location weights (res_gen); TTS_RB_GENERAL=0 keeps those
+    // configurations on the routing without them (serial batch-1 calls or multi-launch; A/B, tests)
+    if (resident_batch_general(gen) && (!d->res_gen || env_is("TTS_RB_GENERAL", '0'))) return TTS_OK;
     if (!(d->cfg.max_batch >= 2 && resident_batch_supports(gen) && !env_is("TTS_RESIDENT_BATCH", '0') &&
           resident_batch_prepare() == hipSuccess))
         return TTS_OK;
@@ -529,6 +534,10 @@ tts_status create_weights(tts_decoder* d, const WeightMap& wm, SrcWeights& w, hi
         if (d->resident && d->res_gen) {
             TTS_TRY(d->dev.alloc(&d->loc_conv_p, 2 * NLOC * 32));
             TTS_HIP(resident_pack_location(d->loc_conv, d->loc_conv_p, s));
+        }
+        if (d->rbatch && resident_batch_general(d->rb_gen)) {
+            TTS_TRY(d->dev.alloc(&d->rb_loc, RB_LOC_FLOATS));
+            TTS_HIP(resident_batch_pack_location(d->loc_conv, d->loc_dense, d->rb_loc, s));
         }
     }
     return TTS_OK;
@@ -735,6 +744,10 @@ void fill_batch_args(const tts_decoder* d, const RunCtx& c, int g0, int nb, ResB
     rb.mel_hist = d->mel_hist + (size_t)g0 * d->hist_cap * d->nmel;
     rb.stop_hist = d->stop_hist + (size_t)g0 * d->hist_cap;
     rb.align_hist = d->align_hist + (size_t)g0 * d->hist_cap * c.Lmax;
+    rb.ta_w = d->ta_w; rb.ta_b = d->ta_b;
+    rb.att_w0 = d->att_w + (size_t)g0 * d->Lcap; rb.att_cum0 = d->att_cum + (size_t)g0 * d->Lcap;
+    rb.win0 = d->win_idx + g0;
+    rb.loc_conv = d->rb_loc; rb.loc_dense = d->rb_loc ? d->rb_loc + RB_LOC_CONV_FLOATS : nullptr;
     rb.gran = d->rb_gran;
     static const int rb_hatt = env_int("TTS_RB_SLEEP_HATT", 0), rb_hdec = env_int("TTS_RB_SLEEP_HDEC", 0),
                      rb_pre2 = env_int("TTS_RB_SLEEP_PRE2", 0), rb_ctx = env_int("TTS_RB_SLEEP_CTX", 0);
@@ -754,7 +767,7 @@ tts_status report_rb_prof(const long long* prof, int nb) {
             pk[RB_PROF_SLOTS - 1]);
     for (int w = 0; w < 4; ++w) {
         fprintf(stderr, "[tts]  wave %d:", w);
-        for (int k : {0, 1, 2, 3, 4, 5, 6, 20, 21, 22, 23, 7, 8, 9, 10, 11, 12}) {
+        for (int k : {0, 1, 2, 3, 4, 5, 6, 20, 21, 22, 23, 7, 8, 9, 10, 19, 11, 12}) {
             double mn = 1e30, mx = 0, sum = 0;
             for (int cu = 0; cu < RES_CUS; ++cu) {
                 const double v = at(cu, w, k) * 0.01 / steps;

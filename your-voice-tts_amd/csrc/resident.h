@@ -189,14 +189,28 @@ struct ResBatchArgs {
     int* status;
     int sleep_hatt, sleep_hdec, sleep_pre2, sleep_ctx;  // s_sleep(4) counts before a gather's first poll (TTS_RB_SLEEP_*)
     long long* prof;           // [256 CU][4 waves][RB_PROF_SLOTS] phase clocks (TTS_RB_PROF=1), else null
+    // general attention form (GEN_TA / GEN_LOCATION / GEN_WINDOW), as ResArgs' fields, per sentence
+    const float* ta_w;         // transition agent [ENC + HATT] and bias [1]
+    const float* ta_b;
+    const float* att_w0;       // initial attention_weights / attention_weights_cum [B][Lcap]
+    const float* att_cum0;
+    const int* win0;           // initial win_idx [B]
+    const float* loc_conv;     // location_conv / location_dense packed by resident_batch_pack_location:
+    const float* loc_dense;    // out and out + RB_LOC_CONV_FLOATS (one buffer: the kernel reads both from loc_conv)
 };
-constexpr int RB_PROF_SLOTS = 26;  // [0, 13) phase sums, [13, 19) clocks at step RB_PROF_T, [20, 24) attention sub-phases, [25] steps
+constexpr int RB_LOC_CONV_FLOATS = 2 * NLOC * 32, RB_LOC_FLOATS = RB_LOC_CONV_FLOATS + ADIM * NLOC;
+// [0, 13) phase sums, [13, 19) clocks at step RB_PROF_T, [19] location + agent (general form),
+// [20, 24) attention sub-phases, [25] steps
+constexpr int RB_PROF_SLOTS = 26;
 constexpr int RB_PROF_T = 150;
 void resident_batch_weight_floats(size_t* wa, size_t* wd);
 size_t resident_batch_granules();
 hipError_t resident_batch_pack(const ResSrc& src, float4* wa, float4* wd, hipStream_t s);
+// location_conv.weight [NLOC][2][KLOC] + location_dense.weight [ADIM][NLOC] -> out [RB_LOC_FLOATS]
+hipError_t resident_batch_pack_location(const float* conv, const float* dense, float* out, hipStream_t s);
 hipError_t resident_batch_prepare();
 bool resident_batch_supports(int gen);
+bool resident_batch_general(int gen);  // the configuration runs the general-attention instantiations
 hipError_t launch_resident_batch(const ResBatchArgs& a, hipStream_t s, bool* launched);
 
 }  // namespace tts

@@ -26,9 +26,13 @@
 // then the context of the CU's 16 channels.  Two device-wide edges per step (h_att, h_dec).
 //
 // Scope: 2 <= B <= RB_MAXB per launch (a larger request runs consecutive launches), every
-// L_b <= 256, nmel <= 256, the attention configurations without location features, windowing or
-// transition agent (forward attention with or without the eval mask, sigmoid or softmax:
-// synthesize.py's and Synthesizer.tts()'s); the others run multi-launch.
+// L_b <= 256, nmel <= 256, every Tacotron2 attention configuration.  Those without location
+// features, windowing or transition agent (forward attention with or without the eval mask, sigmoid
+// or softmax: synthesize.py's and Synthesizer.tts()'s) run resident_batch_kernel<., ., false>; the
+// others (among them the constructor default, location-sensitive + softmax) the general form
+// <., ., true>, which adds per-sentence state to the attention wave: the windowing index, the
+// cumulative weights (a padded LDS row) and, computed for the next step while the h_dec hand-off is
+// in flight, the location term of the wave's positions and the transition agent's u.
 #include "handoff.h"
 #include "resident.h"
 
@@ -57,7 +61,7 @@ constexpr int RBG_TOTAL = RBG_X + 8 * RBX_SIZE;
 static_assert(RBX_SIZE % 16 == 0 && RBG_X % 16 == 0, "pair loads need 16-byte aligned blocks");
 static_assert(RB_MAXB <= 4 && RB_MAXB % 2 == 0, "one attention wave per sentence; flags read in pairs");
 
-template <int NB>
+template <int NB, bool GEN = false>
 struct Lds {
     static constexpr int XHATT = 0;
     static constexpr int XHDEC = XHATT + NB * HATT;
@@ -73,8 +77,11 @@ struct Lds {
     static constexpr int ENCS = INTS + 32;                 // [NB][ENC_L][16] the CU's context channels
     static constexpr int WDC = ENCS + NB * ENC_L * 16;     // [8][256 threads] float4: decoder LSTM ctx part
     static constexpr int WQ = WDC + 8 * RB_THREADS * 4;    // [4 waves][1024] the waves' query rows
-    static constexpr int TOTAL = WQ + 4 * HATT;
+    static constexpr int GCUM = WQ + 4 * HATT;             // general form: [NB][GW_PAD] cumulative weights, zero-padded
+    static constexpr int TOTAL = GCUM + (GEN ? NB * GW_PAD : 0);
 };
+static_assert(Lds<4, true>::TOTAL * sizeof(float) <= 160 * 1024 && Lds<2, true>::TOTAL * sizeof(float) <= 160 * 1024,
+              "the general form's LDS image fits a CU");
 
 // The transpose reduction: V values per lane summed over the 64 lanes of the wave; lane l ends with
 // the total of value index l >> (6 - log2 V).  Each level halves the values a lane keeps: it keeps
@@ -186,9 +193,11 @@ __device__ __forceinline__ bool gather_pairs(__amdgpu_buffer_rsrc_t r, int base,
     }
 }
 
-template <int NB, bool PROF>
+// GEN: the general attention form (location features, windowing, transition agent); the other
+// instantiations carry none of its code.
+template <int NB, bool PROF, bool GEN = false>
 __global__ __launch_bounds__(RB_THREADS, 1) void resident_batch_kernel(const ResBatchArgs a) {
-    using S = Lds<NB>;
+    using S = Lds<NB, GEN>;
     constexpr int V = 4 * NB;  // partial sums per lane (sentence x gate)
     const int c = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -336,6 +345,14 @@ __global__ __launch_bounds__(RB_THREADS, 1) void resident_batch_kernel(const Res
     float gu = 0.5f, vb = 0.f;
     float2 gv = float2{0.f, 0.f};
     int gn = 1;
+    // general form: windowing index, transition agent bias, sentence ab's cumulative weights, the
+    // location term of the wave's positions rank + 32 i at this lane's dims
+    int gwin = -1;
+    float gtb = 0.f;
+    float* gcum = sm + S::GCUM + (GEN && att_w ? ab : 0) * GW_PAD;
+    float2 gl[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) gl[i] = float2{0.f, 0.f};
     if (att_w && Lb > 0) {
         gu = a.u[ab];
         gn = a.nidx[ab];
@@ -350,6 +367,18 @@ __global__ __launch_bounds__(RB_THREADS, 1) void resident_batch_kernel(const Res
         float* es = sm + S::ENCS + ab * S::ENC_L * 16;
         const float* src = a.enc + (size_t)ab * a.Lcap * ENC + 16 * rank;
         for (int k = lane; k < min(Lb, S::ENC_L) * 16; k += 64) es[k] = src[(size_t)(k >> 4) * ENC + (k & 15)];
+        if constexpr (GEN) {
+            // row [1] starts as the initial attention_weights (the location input of step 0, which
+            // then overwrites it); the cumulative weights in their own padded row
+            if (gf & GEN_WINDOW) gwin = a.win0[ab];
+            if (gf & GEN_TA) gtb = a.ta_b[0];
+            for (int k = lane; k < GW_PAD; k += 64) {
+                const int j = k - 16;
+                const bool ok = j >= 0 && j < Lb && (gf & GEN_LOCATION);
+                if (ok) gw[(ab * 2 + 1) * GW_PAD + k] = a.att_w0[(size_t)ab * a.Lcap + j];
+                gcum[k] = ok ? a.att_cum0[(size_t)ab * a.Lcap + j] : 0.f;
+            }
+        }
     } else if (att_w) {
         for (int k = lane; k < 2 * GW_PAD; k += 64) gw[ab * 2 * GW_PAD + k] = 0.f;
     }
@@ -366,6 +395,64 @@ __global__ __launch_bounds__(RB_THREADS, 1) void resident_batch_kernel(const Res
         const bool on = att_w && pe < Lb;
         gp[i].x = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rpt, on ? (2 * lane * a.Lcap + pe) * 4 : OOB_OFF, 0, 0));
         gp[i].y = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rpt, on ? ((2 * lane + 1) * a.Lcap + pe) * 4 : OOB_OFF, 0, 0));
+    }
+    // location_conv (2 -> 32 filters, 31 taps, pad 15) over [weights; cumulative weights] (padded LDS
+    // rows), then location_dense (32 -> 128) at dims 2 lane, 2 lane + 1 (common_layers.py:86-104,
+    // 166-171) for the wave's npos positions.  Lane (f = lane & 31, channel lane >> 5) sums its 31
+    // taps (one load of its taps serves every position), the channels meet by a lane swap; then the
+    // dense rows go by once, each quarter over every position.  Float order per position and dim as
+    // in the batch-1 form (resident_decoder.hip gen_location).
+    // The weights come from L2 in their own packing (rb_pack_loc: register j of lane l at float4
+    // j * 64 + l, so a load instruction reads 1 KB in a row; a lane's 32 consecutive floats of the
+    // batch-1 layouts are 64 cache lines per instruction) and in one round trip, with whatever
+    // `more` loads (the agent's row).  The positions are a rolled loop: unrolled, with a branch per
+    // position, the step's code grew by half and cost 4 us per step, which the h_dec edge (2.6 us
+    // of waiting in the mask-off form) did not hide.
+    const int npos = GEN ? __builtin_amdgcn_readfirstlane(att_w && Lb > rank ? min(8, (Lb - rank + 31) / 32) : 0) : 0;
+    auto location_terms = [&](const float* wrow, auto&& more) {
+        const float* src = (lane < 32 ? wrow : gcum) + rank + 1;  // cat[c][pe + k - 15] = src[k] at position pe = rank + 32 i
+        // (buffer loads: one lane offset and a constant per register, no 64-bit address per 4 KB)
+        const auto rloc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.loc_conv), (short)0, RB_LOC_FLOATS * 4, 0x00020000);
+        auto wl = [&](int j) {  // float4 j of this lane: taps j < 8, dense rows 2 lane / 2 lane + 1 from 8 / 16
+            return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rloc, lane * 16, j * 1024, 0));
+        };
+        float4 wc[8], u0[8], u1[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            wc[q] = wl(q);
+            u0[q] = wl(8 + q);
+            u1[q] = wl(16 + q);
+        }
+        more();
+#pragma unroll 1
+        for (int i = 0; i < npos; ++i, src += 32) {
+            float sacc = 0.f;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                sacc = fmaf(wc[q].x, src[4 * q], sacc);
+                sacc = fmaf(wc[q].y, src[4 * q + 1], sacc);
+                sacc = fmaf(wc[q].z, src[4 * q + 2], sacc);
+                sacc = fmaf(wc[q].w, src[4 * q + 3], sacc);
+            }
+            const float tot = xlevel<32>(sacc, sacc);  // lane f < 32: filter f
+            float l0 = 0.f, l1 = 0.f;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const float f0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tot), 4 * q));
+                const float f1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tot), 4 * q + 1));
+                const float f2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tot), 4 * q + 2));
+                const float f3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tot), 4 * q + 3));
+                l0 = fmaf(u0[q].x, f0, l0); l0 = fmaf(u0[q].y, f1, l0); l0 = fmaf(u0[q].z, f2, l0); l0 = fmaf(u0[q].w, f3, l0);
+                l1 = fmaf(u1[q].x, f0, l1); l1 = fmaf(u1[q].y, f1, l1); l1 = fmaf(u1[q].z, f2, l1); l1 = fmaf(u1[q].w, f3, l1);
+            }
+            // (the term of position i: selects, the array stays in registers)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) gl[k] = k == i ? float2{l0, l1} : gl[k];
+        }
+    };
+    if constexpr (GEN) {
+        // step 0's term from the initial weights (this wave's own LDS writes: in order)
+        if ((gf & GEN_LOCATION) && npos > 0) location_terms(gw + (ab * 2 + 1) * GW_PAD, [] {});
     }
     const auto rg = __builtin_amdgcn_make_buffer_rsrc(a.gran, (short)0, 2 * RBG_TOTAL * 8, 0x00020000);
     const int xb = RBG_X + xcc * RBX_SIZE;  // this XCD's block (the parity offset is added per step)
@@ -499,8 +586,9 @@ __global__ __launch_bounds__(RB_THREADS, 1) void resident_batch_kernel(const Res
             if ((lane & (SQ - 1)) == 0) publish_xcd(G + xb + RBX_Q + (lane / SQ) * ADIM + qrow, E + 3, r);
         }
         mark(6);
-        // 7) attention of sentence ab in wave ab (common_layers.py:166-256 without location / windowing /
-        //    transition agent), the context of this CU's 16 channels, XCD-local publish
+        // 7) attention of sentence ab in wave ab (common_layers.py:166-256; location term, windowing and
+        //    cumulative weights in the general form only), the context of this CU's 16 channels,
+        //    XCD-local publish
         if (att_w && Lb == 0) {  // a padding sentence: zero context (every CU's gather waits for it)
             if (lane < 16) publish_xcd(G + xb + RBX_CTX + ab * ENC + 16 * rank + lane, E + 4, 0.f);
             if (rank == 0 && lane == 16) publish_xcd(G + xb + RBX_TAIL + ab, E + 4, 0.f);
@@ -515,7 +603,12 @@ __global__ __launch_bounds__(RB_THREADS, 1) void resident_batch_kernel(const Res
             {
                 float ev[8];
 #pragma unroll
-                for (int i = 0; i < 8; ++i) ev[i] = gv.x * tanh_fast(q.x + gp[i].x) + gv.y * tanh_fast(q.y + gp[i].y);
+                for (int i = 0; i < 8; ++i) {
+                    if constexpr (GEN)  // v . tanh(q + location + P) + b_v (a zero term without location features)
+                        ev[i] = gv.x * tanh_fast((q.x + gl[i].x) + gp[i].x) + gv.y * tanh_fast((q.y + gl[i].y) + gp[i].y);
+                    else
+                        ev[i] = gv.x * tanh_fast(q.x + gp[i].x) + gv.y * tanh_fast(q.y + gp[i].y);
+                }
                 const float r = xreduce<8>(ev);  // lane 8 i: position rank + 32 i
                 const int pe = rank + 32 * (lane >> 3);
                 if ((lane & 7) == 0 && pe < Lb) publish_xcd(G + xb + RBX_E + ab * RES_LMAX + pe, E + 7, r + vb);
@@ -541,6 +634,26 @@ __global__ __launch_bounds__(RB_THREADS, 1) void resident_batch_kernel(const Res
                 in[i] = ps[i] < Lb;
                 if (!in[i]) e[i] = -INFINITY;
             }
+            if constexpr (GEN) {
+                if (gf & GEN_WINDOW) {
+                    // eval windowing (common_layers.py:184-197)
+                    const int back = gwin - 2, front = gwin + 6;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (in[i] && ((back > 0 && ps[i] < back) || (front < Lb && ps[i] >= front))) e[i] = -INFINITY;
+                    if (gwin == -1) {
+                        const float m = wave_max_dpp(fmaxf(fmaxf(e[0], e[1]), fmaxf(e[2], e[3])));
+                        if (lane == 0) e[0] = m;
+                    }
+                    float bv = e[0];
+                    int bi = ps[0];
+#pragma unroll
+                    for (int i = 1; i < 4; ++i)
+                        if (e[i] > bv) { bv = e[i]; bi = ps[i]; }
+                    wave_argmax(bv, bi);
+                    gwin = __builtin_amdgcn_readfirstlane(bi);
+                }
+            }
             float al[4];
             if (gf & GEN_SOFTMAX) {
                 const float m = wave_max_dpp(fmaxf(fmaxf(e[0], e[1]), fmaxf(e[2], e[3])));
@@ -554,6 +667,15 @@ __global__ __launch_bounds__(RB_THREADS, 1) void resident_batch_kernel(const Res
                 const float S_ = wave_sum_dpp((al[0] + al[1]) + (al[2] + al[3]));
 #pragma unroll
                 for (int i = 0; i < 4; ++i) al[i] = al[i] / S_;
+            }
+            if constexpr (GEN) {
+                if (gf & GEN_LOCATION) {  // update_location_attention (:163-164), this lane's positions
+                    float2* c01 = reinterpret_cast<float2*>(gcum + 16 + 2 * lane);
+                    float2* c23 = reinterpret_cast<float2*>(gcum + 16 + 128 + 2 * lane);
+                    const float2 o01 = *c01, o23 = *c23;
+                    *c01 = float2{o01.x + al[0], o01.y + al[1]};
+                    *c23 = float2{o23.x + al[2], o23.y + al[3]};
+                }
             }
             const float* wold = gw + (ab * 2 + (t & 1)) * GW_PAD + 16;
             float* wnew = gw + (ab * 2 + ((t & 1) ^ 1)) * GW_PAD + 16;
@@ -677,6 +799,36 @@ __global__ __launch_bounds__(RB_THREADS, 1) void resident_batch_kernel(const Res
             }
         }
         mark(10);
+        if constexpr (GEN) {
+            // off the critical path (the h_dec edge is in flight): sentence ab's next-step location
+            // term from this step's weights, and the transition agent's u = sigmoid(ta([ctx_t, h_att_t]))
+            // (common_layers.py:220-222) from the LDS copies every CU holds.  Ahead of the prenet-1
+            // row loads: their 48 registers beside the location weights' 96 spilled.
+            if (att_w && Lb > 0) {
+                float4 twv[6];  // the agent's row at k = 256 q + 4 lane ..
+                bool have_tw = false;
+                auto load_tw = [&] {
+                    if (gf & GEN_TA) {
+                        const float4* tw = reinterpret_cast<const float4*>(a.ta_w) + lane;
+#pragma unroll
+                        for (int q = 0; q < 6; ++q) twv[q] = tw[64 * q];
+                        have_tw = true;
+                    }
+                };
+                if ((gf & GEN_LOCATION) && npos > 0) location_terms(gw + (ab * 2 + ((t & 1) ^ 1)) * GW_PAD, load_tw);
+                if (!have_tw) load_tw();
+                if (gf & GEN_TA) {
+                    float pta = 0.f;
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) pta = dot4(twv[q], ld4(xctx + ab * ENC + 256 * q + 4 * lane), pta);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) pta = dot4(twv[2 + q], ld4(xh_att + ab * HATT + 256 * q + 4 * lane), pta);
+                    gu = sigmoidf_(wave_sum_dpp(pta) + gtb);
+                }
+            }
+            asm volatile("" ::: "memory");
+            mark(19);
+        }
         // 11) gather h_dec_t (this wave's prenet-1 row weights of step 12 in flight meanwhile)
         float4 w1p[12];
 #pragma unroll
@@ -819,6 +971,22 @@ __global__ void rb_pack_wd(const float* wih, const float* whh, float4* out) {
     out[idx] = float4{v[0], v[1], v[2], v[3]};
 }
 
+// location_conv.weight [NLOC][2][KLOC] and location_dense.weight [ADIM][NLOC] for the general
+// form's attention waves: float4 j of lane l at j * 64 + l.  Taps: lane = channel * 32 + filter,
+// j = tap quarter (tap 31 a zero); dense rows 2 l (j < 8) and 2 l + 1 (j >= 8), quarter j & 7.
+__global__ void rb_pack_loc(const float* conv, const float* dense, float* out) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= RB_LOC_FLOATS) return;
+    const int e = idx & 3, l = (idx >> 2) & 63;
+    if (idx < 2 * NLOC * 32) {
+        const int k = 4 * (idx >> 8) + e, f = l & 31, ch = l >> 5;
+        out[idx] = k < KLOC ? conv[(f * 2 + ch) * KLOC + k] : 0.f;
+    } else {
+        const int j = (idx - 2 * NLOC * 32) >> 8;
+        out[idx] = dense[(2 * l + (j >> 3)) * NLOC + 4 * (j & 7) + e];
+    }
+}
+
 int rb_nb(int B) { return B <= 2 ? 2 : 4; }
 
 }  // namespace
@@ -837,25 +1005,42 @@ hipError_t resident_batch_pack(const ResSrc& s, float4* wa, float4* wd, hipStrea
     return hipGetLastError();
 }
 
-size_t resident_batch_smem_bytes(int B) {
-    return (size_t)(rb_nb(B) == 2 ? Lds<2>::TOTAL : Lds<4>::TOTAL) * sizeof(float);
+constexpr int GEN_GENERAL = GEN_TA | GEN_LOCATION | GEN_WINDOW;  // what the general instantiations add
+
+hipError_t resident_batch_pack_location(const float* conv, const float* dense, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(rb_pack_loc, dim3((RB_LOC_FLOATS + 255) / 256), dim3(256), 0, s, conv, dense, out);
+    return hipGetLastError();
+}
+
+size_t resident_batch_smem_bytes(int B, bool general) {
+    const int n = rb_nb(B) == 2 ? (general ? Lds<2, true>::TOTAL : Lds<2>::TOTAL)
+                                : (general ? Lds<4, true>::TOTAL : Lds<4>::TOTAL);
+    return (size_t)n * sizeof(float);
 }
 
 hipError_t resident_batch_prepare() {
     const void* fns[] = {reinterpret_cast<const void*>(&resident_batch_kernel<2, false>),
                          reinterpret_cast<const void*>(&resident_batch_kernel<4, false>),
                          reinterpret_cast<const void*>(&resident_batch_kernel<2, true>),
-                         reinterpret_cast<const void*>(&resident_batch_kernel<4, true>)};
-    const int nbs[] = {2, 4, 2, 4};
-    for (int i = 0; i < 4; ++i) {
+                         reinterpret_cast<const void*>(&resident_batch_kernel<4, true>),
+                         reinterpret_cast<const void*>(&resident_batch_kernel<2, false, true>),
+                         reinterpret_cast<const void*>(&resident_batch_kernel<4, false, true>),
+                         reinterpret_cast<const void*>(&resident_batch_kernel<2, true, true>),
+                         reinterpret_cast<const void*>(&resident_batch_kernel<4, true, true>)};
+    const int nbs[] = {2, 4, 2, 4, 2, 4, 2, 4};
+    for (int i = 0; i < 8; ++i) {
         hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)resident_batch_smem_bytes(nbs[i]));
+                                           (int)resident_batch_smem_bytes(nbs[i], i >= 4));
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
-bool resident_batch_supports(int gen) { return gen != 0 && !(gen & (GEN_TA | GEN_LOCATION | GEN_WINDOW)); }
+bool resident_batch_supports(int gen) {
+    // every combination the batch-1 general form serves (the transition agent belongs to forward attention)
+    return gen != 0 && (!(gen & GEN_TA) || (gen & GEN_FORWARD));
+}
+bool resident_batch_general(int gen) { return (gen & GEN_GENERAL) != 0; }
 
 hipError_t launch_resident_batch(const ResBatchArgs& a, hipStream_t s, bool* launched) {
     *launched = false;
@@ -863,15 +1048,26 @@ hipError_t launch_resident_batch(const ResBatchArgs& a, hipStream_t s, bool* lau
         return hipErrorInvalidValue;
     for (int b = 0; b < a.B; ++b)
         if (a.L[b] < 2 || a.L[b] > RES_LMAX || a.L[b] > a.Lcap) return hipErrorInvalidValue;
+    if ((a.gen & GEN_TA) && !(a.ta_w && a.ta_b)) return hipErrorInvalidValue;
+    if ((a.gen & GEN_LOCATION) && !(a.att_w0 && a.att_cum0 && a.loc_conv && a.loc_dense == a.loc_conv + RB_LOC_CONV_FLOATS))
+        return hipErrorInvalidValue;
+    if ((a.gen & GEN_WINDOW) && !a.win0) return hipErrorInvalidValue;
     ResBatchArgs arg = a;
     for (int b = a.B; b < RB_MAXB; ++b) arg.L[b] = 0;
     void* args[] = {&arg};
     const bool prof = a.prof != nullptr;
+    const bool general = resident_batch_general(a.gen);
     const void* fn = rb_nb(a.B) == 2 ? (prof ? reinterpret_cast<const void*>(&resident_batch_kernel<2, true>)
                                              : reinterpret_cast<const void*>(&resident_batch_kernel<2, false>))
                                      : (prof ? reinterpret_cast<const void*>(&resident_batch_kernel<4, true>)
                                              : reinterpret_cast<const void*>(&resident_batch_kernel<4, false>));
-    return launch_persistent(fn, dim3(RES_CUS), dim3(RB_THREADS), args, resident_batch_smem_bytes(a.B), s, launched);
+    if (general)
+        fn = rb_nb(a.B) == 2 ? (prof ? reinterpret_cast<const void*>(&resident_batch_kernel<2, true, true>)
+                                     : reinterpret_cast<const void*>(&resident_batch_kernel<2, false, true>))
+                             : (prof ? reinterpret_cast<const void*>(&resident_batch_kernel<4, true, true>)
+                                     : reinterpret_cast<const void*>(&resident_batch_kernel<4, false, true>));
+    return launch_persistent(fn, dim3(RES_CUS), dim3(RB_THREADS), args, resident_batch_smem_bytes(a.B, general), s,
+                             launched);
 }
 
 }  // namespace tts

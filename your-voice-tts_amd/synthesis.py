@@ -81,8 +81,10 @@ def _resident_batch(model, ids_list):
 
 def _serial_eligible(model, ids_list):
     """Whether a request decodes serially on the resident batch-1 decoder: 2..SERIAL_RESIDENT_MAX
-    sentences the batch decoder does not take, each within the length the handle's resident
-    decoder serves now (tts_decoder_resident_limits: no hard-coded limit here)."""
+    sentences the batch decoder does not take (it takes every attention configuration; a handle
+    without it was created under TTS_RESIDENT_BATCH=0 / TTS_RB_GENERAL=0 or gave it up after a
+    refused launch), each within the length the handle's resident decoder serves now
+    (tts_decoder_resident_limits: no hard-coded limit here)."""
     B = len(ids_list)
     if B < 2 or B > SERIAL_RESIDENT_MAX:
         return False

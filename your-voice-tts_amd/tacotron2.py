@@ -415,7 +415,8 @@ class Tacotron2:
 
     def resident_limits(self, Lmax=1):
         """(max sentences, max encoder length) the resident decoder serves on this handle now
-        (tts_decoder_resident_limits; (0, 0): multi-launch only)."""
+        (tts_decoder_resident_limits; (0, 0): multi-launch only).  Up to 8 sentences under every
+        attention configuration, location features / windowing / transition agent included."""
         lib, hdec, _ = self._handles(max(int(Lmax), 1), 1)
         mb, ml = ctypes.c_int(), ctypes.c_int()
         _native.check(lib.tts_decoder_resident_limits(hdec, ctypes.byref(mb), ctypes.byref(ml)),
