@@ -120,7 +120,8 @@ struct ResArgs {
     float* stop_hist;
     float* align_hist;
     unsigned long long* gran;  // [2][GR_TOTAL], zeroed before every launch
-    int* status;               // [0]: 0 ok, else the id of the wait that timed out
+    int* status;               // [0]: 0 ok, else the id of the wait that timed out (9: the stop lane's
+                               // own wait for the tail granule, synthesis form)
     // s_sleep(4) counts (~0.12 us each) before the first poll of a gather: a poll storm from every CU
     // slows the hand-off it waits for (device-wide h_att / h_dec; XCD-local pre1, prenet-2, context)
     int sleep_hatt, sleep_hdec, sleep_p1, sleep_pre2, sleep_ctx;

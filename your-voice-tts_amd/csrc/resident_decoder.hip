@@ -7,10 +7,11 @@
 //   3. prenet part, row sums, LSTM cell of units 4c..4c+3, publish h_att_t   (tacotron2.py:195-197)
 //   4. gather h_att_t; 5. CUs < 128: query row c, publish                     (common_layers.py:179)
 //   6. decoder-LSTM partial over [h_att_t | h_dec_{t-1}]                  (LDS weights)
-//   7. CU 255: energies, sigmoid, forward attention + mask, context, publish ctx_t and the tail
+//   7. CU 255: energies, sigmoid, forward attention + mask, context, publish ctx_t, then the tail
 //      (common_layers.py:178-182, 199-223, 239-253)
 //   8. gather ctx_t; 9. context part, cell, publish h_dec_t               (tacotron2.py:206-208)
-//  10. gather h_dec_t (the prenet-1 row weights of step 11 in flight from the XCD's L2);
+//  10. gather h_dec_t (the prenet-1 row weights of step 11 in flight from the XCD's L2; the stop
+//      lane's load of the tail granule too: nobody else reads the tail);
 //  11. every wave: one folded prenet-1 row of this XCD's copy -> XCD-local publish; the XCD's
 //      stop CU (rank 0), wave 3: the stop row -> sigmoid + stop rule -> XCD-local continue flag
 //      (tacotron2.py:214-224, 256-277).  Mel row c of step t is written by wave 4 during step
@@ -50,6 +51,11 @@ __device__ __forceinline__ float dot4(float4 w, float4 x, float acc) {
     return fmaf(w.w, x.w, acc);
 }
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+// Keeps four loaded float4 live at one point: the loads that fill them all issue before it
+__device__ __forceinline__ void pin4(float4& a, float4& b, float4& c, float4& d) {
+    asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w), "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.w), "+v"(c.x),
+                 "+v"(c.y), "+v"(c.z), "+v"(c.w), "+v"(d.x), "+v"(d.y), "+v"(d.z), "+v"(d.w));
+}
 // Sums over each half-wave (lanes 0-31, 32-63) by DPP row scans: the totals land in lanes 31
 // and 63 (other lanes hold partial scans).  No LDS round trip per level.
 __device__ __forceinline__ float sum32_dpp(float v) {
@@ -134,17 +140,26 @@ __device__ __forceinline__ float res_context(const ResWin& w, float wcx, const f
     ctx = w.post ? ctx + px : ctx;
     return ctx;
 }
-// The weight at position p (0 outside the window)
+// The weight at position p (0 outside the window), by selects.  SEL: for a wave-uniform p (the
+// tail's L-2, L-1) the compiler turns the lookup into a chain of scalar branches; the empty asm
+// moves the offset into a vector register, so it stays compares and selects there too
+template <bool SEL = false>
 __device__ __forceinline__ float res_weight_at(const ResWin& w, float wcx, const float (&ww)[4], int p) {
-    const int d = p - w.clo;
-    const float v = d == 0 ? ww[0] : d == 1 ? ww[1] : d == 2 ? ww[2] : ww[3];
-    return p == w.cx ? wcx : ((p >= w.clo && p <= w.chi) ? v : 0.f);
+    int d = p - w.clo;
+    if (SEL) asm volatile("" : "+v"(d));
+    const float w0 = ww[0], w1 = ww[1], w2 = ww[2], w3 = ww[3];
+    float v = w0;
+    v = d == 1 ? w1 : v;
+    v = d == 2 ? w2 : v;
+    v = d >= 3 ? w3 : v;
+    v = (d >= 0 && p <= w.chi) ? v : 0.f;
+    return p == w.cx ? wcx : v;
 }
 // What the step leaves for later ones: the stop rule's tail alpha[L-2] + alpha[L-1]
 // (tacotron2.py:268) and the next step's n = argmax(prev_alpha) = 1 + the first argmax of
 // alpha[0..L-2] (0 when all zero), slots visited in position order.
 __device__ __forceinline__ int res_tail_next(const ResWin& w, float wcx, const float (&ww)[4], int L, float& tail) {
-    tail = res_weight_at(w, wcx, ww, L - 2) + res_weight_at(w, wcx, ww, L - 1);
+    tail = res_weight_at<true>(w, wcx, ww, L - 2) + res_weight_at<true>(w, wcx, ww, L - 1);
     float bv = 0.f;
     int bi = -1;
     auto consider = [&](bool present, int p, float wp) {
@@ -185,7 +200,7 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
     float4* wdl = reinterpret_cast<float4*>(sm);  // [16 i4][16 r][32 ks]
     float* xh_att = sm + SM_WDL;
     float* xh_dec = xh_att + HATT;
-    float* xctx = xh_dec + HDEC;  // [ENC] context, [ENC] = stop-rule tail
+    float* xctx = xh_dec + HDEC;  // [ENC] context, [ENC] = stop-rule tail (general form)
     float* xpre = xctx + ENC + 16;
     float* xq = xpre + PRE;
     float* gates = xq + ADIM;  // [16]
@@ -476,6 +491,13 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
     int t = 0;
     for (;; ++t) {
         u64* G = a.gran + (t & 1) * GR_TOTAL;          // this step's granules
+        // this XCD's slots of them: the synthesis form addresses them from G (four pointer pairs
+        // fewer live across the loop); the general form keeps its own base pointers (with offsets
+        // it spilled more and lost 3 %)
+        u64* const gxs = GEN ? Gx + (t & 1) * GR_TOTAL : G + s_x;
+        u64* const gqs = GEN ? Gq + (t & 1) * GR_TOTAL : G + s_q;
+        u64* const gcs = GEN ? Gc + (t & 1) * GR_TOTAL : G + s_c;
+        u64* const g1s = GEN ? G1 + (t & 1) * GR_TOTAL : G + s_1;
         // tags E+1 .. E+7 (never 0): the step count wraps at 2048 inside its 11 bits (a granule
         // slot is rewritten every second step, so only step t-2's tag can be stale there; runs
         // reach the Synthesizer's 3000-step cap, server/synthesizer.py:66), the previous step's
@@ -531,7 +553,7 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         if (flags[0] | flags[1]) break;
         {
             const float4 x = ld4(xp1 + lane * 4);
-            u64* gx = Gx + (t & 1) * GR_TOTAL;
+            u64* gx = gxs;
             if (has_row) {
                 const float s0 = wave_sum_dpp(dot4(wp0, x, 0.f));
                 if (lane == 0) publish_xcd(gx + r0, E + 1, fmaxf(s0 + bp2, 0.f));
@@ -599,14 +621,33 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
             float s = dot4(wq0, ld4(xh_att + qhalf * 512 + lane * 4), 0.f);
             s = dot4(wq1, ld4(xh_att + qhalf * 512 + 256 + lane * 4), s);
             s = wave_sum_dpp(s);
-            if (lane == 0) publish_xcd(Gq + (t & 1) * GR_TOTAL + 2 * qrow + qhalf, E + 3, s);
+            if (lane == 0) publish_xcd(gqs + 2 * qrow + qhalf, E + 3, s);
             if (tid == 0) { RES_EV(t, 8) }
         }
         // 6) decoder LSTM over h_att_t (its h_dec_{t-1} half ran at the loop top).  The attention CU
         //    too: the query rows are crossing the XCD meanwhile (when this half followed its context
-        //    publish instead, the CU idled here and was then the last to publish h_dec)
+        //    publish instead, the CU idled here and was then the last to publish h_dec): there as
+        //    two rounds of four chunks whose eight LDS reads are in flight together (left to itself
+        //    the compiler waits for every chunk's pair of reads before the next, eight round trips
+        //    ahead of the attention CU's query gather); the other CUs wait for the context anyway
+        if (att_cu) {
+#pragma unroll 1
+            for (int h = 0; h < 8; h += 4) {
+                float4 wv[4], xx[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    wv[j] = wdl[((h + j) * 16 + r) * 32 + ks];
+                    xx[j] = ld4(xh_att + (h + j) * 128 + ks * 4);
+                }
+                pin4(wv[0], wv[1], wv[2], wv[3]);  // the four chunks' eight LDS reads in flight together
+                pin4(xx[0], xx[1], xx[2], xx[3]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc_d = dot4(wv[j], xx[j], acc_d);
+            }
+        } else {
 #pragma unroll 2
-        for (int i = 0; i < 8; ++i) acc_d = dot4(wdl[(i * 16 + r) * 32 + ks], ld4(xh_att + i * 128 + ks * 4), acc_d);
+            for (int i = 0; i < 8; ++i) acc_d = dot4(wdl[(i * 16 + r) * 32 + ks], ld4(xh_att + i * 128 + ks * 4), acc_d);
+        }
         RES_MARK(5);
         float wcx = 0.f, ww[4] = {0.f, 0.f, 0.f, 0.f};  // the step's five weights (ResWin)
         int n_win = 0;  // attention CU: the n they belong to (alpha and the alignment row follow the h_dec publish)
@@ -770,7 +811,7 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
             c0 = wave_sum_dpp(c0);
             c1 = wave_sum_dpp(c1);
             {
-                u64* gcx = Gc + (t & 1) * GR_TOTAL;
+                u64* gcx = gcs;
                 if (lane < 2) publish_xcd(gcx + 16 * rank + 2 * wave + lane, E + 4, lane ? c1 : c0);
                 if (rank == 0 && wave == 0 && lane == 2) publish_xcd(gcx + ENC, E + 4, tail);
             }
@@ -882,15 +923,14 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
             res_weights(win, rm, cw, wcx, ww);
             const float ctx = res_context(win, wcx, ww, ex, erow);
             RES_MARK(15);
-            publish_xcd(Gc + (t & 1) * GR_TOTAL + tid, E + 4, ctx);
+            publish_xcd(gcs + tid, E + 4, ctx);
             xctx[tid] = ctx;  // this CU skips the gather
             if (tid == 0) { RES_EV(t, 11) }
-            // off the chain of the 512 channels: the tail (the stop CU's wave 4 waits for it beside
-            // the context) and, after it, the next step's n
+            // off the chain of the 512 channels: the tail (read by the XCD's stop lane alone, in
+            // step 11; rank 0 is never the attention CU) and, after it, the next step's n
             float tail;
             const int n_next = res_tail_next(win, wcx, ww, L, tail);
-            if (tid == 0) publish_xcd(Gc + (t & 1) * GR_TOTAL + ENC, E + 4, tail);
-            if (tid == 0) xctx[ENC] = tail;
+            if (tid == 0) publish_xcd(gcs + ENC, E + 4, tail);
             RES_MARK(8);
             n_win = n;
             n_prev = n;
@@ -901,19 +941,33 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         float4 w1[6];
 #pragma unroll
         for (int i = 0; i < 6; ++i) w1[i] = ld4(w1p + i * 256);
-        // 8) gather ctx_t and the tail
-        if (wave < 5 && !att_cu) {  // waves 0-3: the 512 context values as pairs; wave 4, lane 0: the tail
+        // 8) gather ctx_t (waves 0-3: the 512 context values as pairs).  The tail, which the
+        //    attention CU publishes after it, is not waited for here: B4, this CU's cell and its
+        //    h_dec publish need the context only
+        if constexpr (GEN) {
+            // (the general form keeps its tail in this gather, wave 4 lane 0: every form of it with
+            // the tail off the gather compiled to more scratch and ran 4 % slower)
+            if (wave < 5) {
+                const int gc = s_c + (t & 1) * GR_TOTAL;
+                for (int i = 0; i < a.sleep_ctx; ++i) __builtin_amdgcn_s_sleep(4);
+                float c0 = 0.f, c1 = 0.f;
+                const bool ok = wave < 4 ? sweep_pair(rg, gc + 2 * pk, true, E + 4, c0, c1, tmo)
+                                         : sweep_pair(rg, lane == 0 ? gc + ENC : -1, false, E + 4, c0, c1, tmo);
+                if (wave < 4) {
+                    xctx[2 * pk] = c0;
+                    xctx[2 * pk + 1] = c1;
+                } else if (lane == 0) {
+                    xctx[ENC] = c0;
+                }
+                if (!ok && lane == 0) { flags[1] = 1; fail(a.status, 4, t); }
+            }
+        } else if (wave < 4 && !att_cu) {
             const int gc = s_c + (t & 1) * GR_TOTAL;
             for (int i = 0; i < a.sleep_ctx; ++i) __builtin_amdgcn_s_sleep(4);
             float c0 = 0.f, c1 = 0.f;
-            const bool ok = wave < 4 ? sweep_pair(rg, gc + 2 * pk, true, E + 4, c0, c1, tmo)
-                                     : sweep_pair(rg, lane == 0 ? gc + ENC : -1, false, E + 4, c0, c1, tmo);
-            if (wave < 4) {
-                xctx[2 * pk] = c0;
-                xctx[2 * pk + 1] = c1;
-            } else if (lane == 0) {
-                xctx[ENC] = c0;
-            }
+            const bool ok = sweep_pair(rg, gc + 2 * pk, true, E + 4, c0, c1, tmo);
+            xctx[2 * pk] = c0;
+            xctx[2 * pk + 1] = c1;
             if (!ok && lane == 0) { flags[1] = 1; fail(a.status, 4, t); }
         }
         __syncthreads();  // B4
@@ -961,6 +1015,13 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
             if (tid < L) anew[tid] = wdef;
             if (att_log && t < a.hist_cap && tid < a.Lalign) a.align_hist[(int64_t)t * a.Lalign + tid] = wdef;
         }
+        // the stop lane's tail granule (tag, value), loaded ahead of the first-poll delay: the
+        // attention CU published it before it reached B4, so step 11 finds it in registers
+        float2 tl = {0.f, 0.f};
+        const int s_tail = s_c + (t & 1) * GR_TOTAL + ENC;
+        if (!GEN && stop_cu && wave == 3)
+            tl = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rg, lane == 0 ? s_tail * 8 : OOB_OFF, 0,
+                                                                                 SC1_VOLATILE));
         // 10) gather h_dec_t
         {
             for (int i = 0; i < a.sleep_hdec; ++i) __builtin_amdgcn_s_sleep(4);
@@ -1003,7 +1064,7 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
                 if (stw) ss = dot4(wsr[i * 64], x, ss);
             }
             s = wave_sum_dpp(s);
-            u64* g1 = G1 + (t & 1) * GR_TOTAL;
+            u64* g1 = g1s;
             if (has_row && lane == 0) {
                 const float p = fmaxf(s + bp1, 0.f);
                 publish_xcd(g1 + r0, E + 6, p);
@@ -1017,7 +1078,12 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
                     // every XCD's stop CU decides identically, the logging XCD writes the outputs
                     const float stv = sigmoidf_(ss + st[49]);
                     if (xlog && t < a.hist_cap) a.stop_hist[t] = stv;
-                    const float tail = xctx[ENC];
+                    // the tail: the early load, or (not yet there) a bounded wait of its own, wait 9
+                    float tail = GEN ? xctx[ENC] : tl.x;
+                    if (!GEN && __float_as_uint(tl.y) != E + 4) {
+                        float unused;
+                        if (!sweep_pair(rg, s_tail, false, E + 4, tail, unused, tmo)) { flags[1] = 1; fail(a.status, 9, t); }
+                    }
                     int* sst = reinterpret_cast<int*>(st);
                     const int f1 = sst[50] | ((tail > 0.8f && t > L) ? 1 : 0);
                     sst[50] = f1;
