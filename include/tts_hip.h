@@ -247,12 +247,34 @@ tts_status tts_gl_save_pcm16(tts_gl* g, const double* wav, int64_t pitch, const 
 /* Mel analysis for GST style wavs: AudioProcessor.melspectrogram (utils/audio.py:146-152) as used by
  * compute_style_mel (utils/synthesis.py:28-35): pre-emphasis FIR, librosa 0.6.2 stft (float64 FFT,
  * complex64 result), |D|, mel projection (float64), amp->dB, _normalize.
- *   mel_basis [host] fp64 [num_mels][n_fft/2+1] (librosa filters.mel), set once per handle
+ *   mel_basis [host] fp64 [num_mels][n_fft/2+1] (librosa filters.mel), set once per handle (each row's
+ *   nonzero bin range is found here and kept on the device for tts_gl_linear_to_mel)
  *   wav [dev] fp64 [B][Nmax]; N [host] int32 [B] (>= 2); mel [dev] fp32 [B][Fmax][num_mels]
  *   (frame-major; sentence b has 1 + N[b]/hop frames, the rest zero). */
 tts_status tts_gl_set_mel_basis(tts_gl* g, const double* mel_basis);
 tts_status tts_gl_melspectrogram(tts_gl* g, const double* wav, const int32_t* N, int B, int64_t Nmax, float* mel,
                                  int Fmax, void* stream);
+
+/* The analysis half of AudioProcessor from one STFT: spectrogram (utils/audio.py:138-144), melspectrogram
+ * (:146-152), or both as collate_fn computes them for every wav (datasets/TTSDataset.py:191-192).  One
+ * launch and one FFT per frame whichever outputs are asked for; at least one must be non-NULL, and `mel`
+ * needs tts_gl_set_mel_basis first.  Bin k of the linear output is 20 log10(max(min_level, |D_k|)) -
+ * ref_level_db through _normalize (all four flags, max_norm), |D_k| the float32 magnitude of the complex64
+ * STFT value; the mel output is bitwise tts_gl_melspectrogram's.
+ *   wav [dev] fp64 [B][Nmax]; N [host] int32 [B] (2 <= N[b] <= Nmax; Fmax >= 1 + N[b]/hop)
+ *   linear [dev] fp32 [B][Fmax][n_fft/2+1] or NULL; mel [dev] fp32 [B][Fmax][num_mels] or NULL
+ *   (frame-major, the layout tts_gl_run(TTS_GL_FROM_LINEAR) reads; rows at and beyond 1 + N[b]/hop zero). */
+tts_status tts_gl_analyze(tts_gl* g, const double* wav, const int32_t* N, int B, int64_t Nmax, float* linear,
+                          float* mel, int Fmax, void* stream);
+
+/* AudioProcessor.out_linear_to_mel (utils/audio.py:174-180): a model's normalised linear spectrogram to the
+ * normalised mel an external vocoder reads, per frame _denormalize -> + ref_level_db -> 10^(x*0.05)
+ * (float32) -> mel_basis . S (float64, summed over each basis row's nonzero bins only) -> _amp_to_db -
+ * ref_level_db -> _normalize.  Needs tts_gl_set_mel_basis first.
+ *   linear [dev] fp32 [B][Fmax][n_fft/2+1]; F [host] int32 [B] (1 <= F[b] <= Fmax)
+ *   mel [dev] fp32 [B][Fmax][num_mels] (rows at and beyond F[b] zero). */
+tts_status tts_gl_linear_to_mel(tts_gl* g, const float* linear, const int32_t* F, int B, int Fmax, float* mel,
+                                void* stream);
 
 /* Time of the last tts_gl_run's iteration loop (ms, GPU) and kernel launches in it. */
 tts_status tts_gl_last_timing(tts_gl* g, float* loop_ms, int* launches);

@@ -30,7 +30,7 @@ EXPORTS = (
     "tts_postnet_create", "tts_postnet_destroy", "tts_postnet_run",
     "tts_gl_create", "tts_gl_destroy", "tts_gl_run", "tts_gl_last_timing", "tts_gl_last_path", "tts_gl_profile",
     "tts_gl_set_mel_basis", "tts_gl_melspectrogram", "tts_gl_set_phase_state", "tts_gl_get_phase_state",
-    "tts_gl_draw_phases", "tts_gl_save_pcm16",
+    "tts_gl_draw_phases", "tts_gl_save_pcm16", "tts_gl_analyze", "tts_gl_linear_to_mel",
     "tts_synth_create", "tts_synth_destroy", "tts_synth_run", "tts_synth_sync",
     "tts_tacotron_create", "tts_tacotron_destroy", "tts_tacotron_encode", "tts_tacotron_decode",
     "tts_tacotron_decode_teacher",
@@ -107,6 +107,8 @@ def _declare(lib):
                                ctypes.c_int, vp, vp]
     lib.tts_gl_set_mel_basis.argtypes = [vp, vp]
     lib.tts_gl_melspectrogram.argtypes = [vp, vp, I32P, ctypes.c_int, ctypes.c_int64, vp, ctypes.c_int, vp]
+    lib.tts_gl_analyze.argtypes = [vp, vp, I32P, ctypes.c_int, ctypes.c_int64, vp, vp, ctypes.c_int, vp]
+    lib.tts_gl_linear_to_mel.argtypes = [vp, vp, I32P, ctypes.c_int, ctypes.c_int, vp, vp]
     lib.tts_gl_last_timing.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]
     U32P = ctypes.POINTER(ctypes.c_uint32)
     lib.tts_gl_set_phase_state.argtypes = [vp, U32P, ctypes.c_int]
@@ -144,7 +146,7 @@ def _declare(lib):
         fn = getattr(lib, name)
         if name.endswith(("_create", "_run", "_timing", "_profile", "_encode", "_decode", "_postnet", "_state",
                           "_continue", "_basis", "_melspectrogram", "_path", "_sync", "_phases", "_teacher",
-                          "_phase_state", "_pcm16", "_limits")):
+                          "_phase_state", "_pcm16", "_limits", "_analyze", "_to_mel")):
             fn.restype = ctypes.c_int
 
 

@@ -1,4 +1,4 @@
-"""Drop-in for the inverse half of the reference ``AudioProcessor`` (utils/audio.py:11-201).
+"""Drop-in for the reference ``AudioProcessor`` (utils/audio.py:11-255).
 
 ``inv_mel_spectrogram`` / ``inv_spectrogram`` keep the reference signatures (numpy [n, T] in,
 numpy float64 waveform out) and run Griffin-Lim on the GPU through libtts_hip ``tts_gl_run``:
@@ -7,6 +7,11 @@ denormalise -> dB->amp -> pinv(mel basis) -> ^power -> GL (librosa 0.6.2 stft/is
 ``np.random.rand(*S.shape)`` exactly as utils/audio.py:183 does, so a caller that seeds numpy gets
 the same phases as the reference.  ``inv_mel_spectrogram_batch`` is the batched GPU-resident form
 (torch tensors in HBM, device-drawn phases) the batched/sharded synthesis uses.
+
+The analysis half runs on the GPU too: ``spectrogram`` / ``melspectrogram`` (``tts_gl_analyze``; both
+from one STFT in ``features_batch``) and ``out_linear_to_mel`` (``tts_gl_linear_to_mel``), with batched
+forms on torch tensors in the frame-major layout Griffin-Lim reads.  The reference's small helpers
+(``_normalize``, ``mulaw_encode``, ``quantize``, ...) are restated in numpy on the host.
 
 The mel filter bank is librosa 0.6.2 ``filters.mel`` (Slaney, area-normalised), restated in
 numpy because librosa is not installed; its pseudo-inverse is computed once in float64 on the
@@ -109,6 +114,57 @@ class AudioProcessor:
 
     def _db_to_amp(self, x):  # utils/audio.py:125-126
         return np.power(10.0, x * 0.05)
+
+    def _linear_to_mel(self, spectrogram):  # utils/audio.py:60-62
+        return np.dot(self._build_mel_basis(), spectrogram)
+
+    def _mel_to_linear(self, mel_spec):  # utils/audio.py:64-66
+        inv_mel_basis = np.linalg.pinv(self._build_mel_basis())
+        return np.maximum(1e-10, np.dot(inv_mel_basis, mel_spec))
+
+    def _normalize(self, S):  # utils/audio.py:79-94
+        if not self.signal_norm:
+            return S
+        S_norm = ((S - self.min_level_db) / - self.min_level_db)
+        if self.symmetric_norm:
+            S_norm = ((2 * self.max_norm) * S_norm) - self.max_norm
+            if self.clip_norm:
+                S_norm = np.clip(S_norm, -self.max_norm, self.max_norm)
+            return S_norm
+        S_norm = self.max_norm * S_norm
+        if self.clip_norm:
+            S_norm = np.clip(S_norm, 0, self.max_norm)
+        return S_norm
+
+    def _amp_to_db(self, x):  # utils/audio.py:121-123
+        min_level = np.exp(self.min_level_db / 20 * np.log(10))
+        return 20 * np.log10(np.maximum(min_level, x))
+
+    def apply_preemphasis(self, x):  # utils/audio.py:128-131
+        if self.preemphasis == 0:
+            raise RuntimeError(" !! Preemphasis is applied with factor 0.0. ")
+        return scipy.signal.lfilter([1, -self.preemphasis], [1], x)
+
+    @staticmethod
+    def mulaw_encode(wav, qc):  # utils/audio.py:219-226
+        mu = 2 ** qc - 1
+        signal = np.sign(wav) * np.log(1 + mu * np.abs(wav)) / np.log(1. + mu)
+        signal = (signal + 1) / 2 * mu + 0.5
+        return np.floor(signal,)
+
+    @staticmethod
+    def mulaw_decode(wav, qc):  # utils/audio.py:228-233
+        mu = 2 ** qc - 1
+        return np.sign(wav) / mu * ((1 + mu) ** np.abs(wav) - 1)
+
+    def encode_16bits(self, x):  # utils/audio.py:248-249
+        return np.clip(x * 2**15, -2**15, 2**15 - 1).astype(np.int16)
+
+    def quantize(self, x, bits):  # utils/audio.py:251-252
+        return (x + 1.) * (2**bits - 1) / 2
+
+    def dequantize(self, x, bits):  # utils/audio.py:254-255
+        return 2 * x / (2**bits - 1) - 1
 
     def apply_inv_preemphasis(self, x):  # utils/audio.py:133-136
         if self.preemphasis == 0:
@@ -246,15 +302,33 @@ class AudioProcessor:
         _native.check(lib.tts_gl_profile(h, int(reps), ms, n), "tts_gl_profile")
         return dict(zip(_native.GL_KERNELS, [float(v) for v in ms]))
 
-    # ---------------------------------------------------------------- mel analysis (GST style wavs)
-    def melspectrogram_batch(self, wav, N):
-        """wav: CUDA float64 [B, Nmax]; N: samples per sentence.  Returns (CUDA float32
-        [B, Fmax, num_mels] frame-major, frames per sentence = 1 + N // hop)."""
+    # ---------------------------------------------------------------- analysis (device)
+    def _set_mel_basis(self):
         lib, h = self._handle()
         if not self._mel_basis_set:
             basis = np.ascontiguousarray(self._build_mel_basis(), dtype=np.float64)
             _native.check(lib.tts_gl_set_mel_basis(h, basis.ctypes.data_as(ctypes.c_void_p)), "tts_gl_set_mel_basis")
             self._mel_basis_set = True
+        return lib, h
+
+    def _analyze(self, wav, N, want_linear, want_mel):
+        """tts_gl_analyze: one STFT per frame, either or both of the outputs (None where not asked)."""
+        lib, h = self._set_mel_basis() if want_mel else self._handle()
+        wav = wav.to(torch.float64).contiguous()
+        B, Nmax = wav.shape
+        F = [1 + int(n) // self.hop_length for n in N]
+        lin = torch.empty(B, max(F), self.n_fft // 2 + 1, device=wav.device) if want_linear else None
+        mel = torch.empty(B, max(F), self.num_mels, device=wav.device) if want_mel else None
+        _native.check(lib.tts_gl_analyze(h, ctypes.c_void_p(wav.data_ptr()), _native.i32_array(N), B, Nmax,
+                                         ctypes.c_void_p(lin.data_ptr()) if want_linear else None,
+                                         ctypes.c_void_p(mel.data_ptr()) if want_mel else None, max(F),
+                                         _native.stream_handle()), "tts_gl_analyze")
+        return mel, lin, F
+
+    def melspectrogram_batch(self, wav, N):
+        """wav: CUDA float64 [B, Nmax]; N: samples per sentence.  Returns (CUDA float32
+        [B, Fmax, num_mels] frame-major, frames per sentence = 1 + N // hop)."""
+        lib, h = self._set_mel_basis()
         wav = wav.to(torch.float64).contiguous()
         B, Nmax = wav.shape
         F = [1 + int(n) // self.hop_length for n in N]
@@ -264,11 +338,49 @@ class AudioProcessor:
                       "tts_gl_melspectrogram")
         return mel, F
 
+    def spectrogram_batch(self, wav, N):
+        """wav: CUDA float64 [B, Nmax]; N: samples per sentence.  Returns (CUDA float32
+        [B, Fmax, num_freq] frame-major, the layout griffin_lim_batch(mode=TTS_GL_FROM_LINEAR) takes,
+        frames per sentence)."""
+        _, lin, F = self._analyze(wav, N, True, False)
+        return lin, F
+
+    def features_batch(self, wav, N):
+        """melspectrogram_batch and spectrogram_batch from one STFT per frame, as collate_fn needs them
+        (datasets/TTSDataset.py:191-192).  Returns (mel, linear, frames per sentence)."""
+        return self._analyze(wav, N, True, True)
+
     def melspectrogram(self, y):  # utils/audio.py:146-152 -> ndarray [num_mels, frames]
         self._handle()  # raises without a GPU / library: no CPU fallback
         y = np.asarray(y, dtype=np.float64)
         mel, F = self.melspectrogram_batch(torch.from_numpy(y).cuda()[None], [len(y)])
         return mel[0, :F[0]].T.double().cpu().numpy()
+
+    def spectrogram(self, y):  # utils/audio.py:138-144 -> ndarray [num_freq, frames]
+        self._handle()  # raises without a GPU / library: no CPU fallback
+        y = np.asarray(y, dtype=np.float64)
+        lin, F = self.spectrogram_batch(torch.from_numpy(y).cuda()[None], [len(y)])
+        return lin[0, :F[0]].T.double().cpu().numpy()
+
+    def out_linear_to_mel_batch(self, linear, frames):
+        """linear: CUDA float32 [B, Fmax, num_freq] (frame-major: a Tacotron's out["linear"], or
+        spectrogram_batch's output); frames: list of F_b.  Returns CUDA float32 [B, Fmax, num_mels],
+        rows at and beyond F_b zero (tts_gl_linear_to_mel)."""
+        lib, h = self._set_mel_basis()
+        linear = linear.float().contiguous()
+        B, Fmax = linear.shape[0], linear.shape[1]
+        mel = torch.empty(B, Fmax, self.num_mels, device=linear.device)
+        _native.check(lib.tts_gl_linear_to_mel(h, ctypes.c_void_p(linear.data_ptr()), _native.i32_array(frames), B,
+                                               Fmax, ctypes.c_void_p(mel.data_ptr()), _native.stream_handle()),
+                      "tts_gl_linear_to_mel")
+        return mel
+
+    def out_linear_to_mel(self, linear_spec):  # utils/audio.py:174-180 -> ndarray [num_mels, T]
+        self._handle()  # raises without a GPU / library: no CPU fallback
+        linear_spec = np.asarray(linear_spec, dtype=np.float32)
+        T = linear_spec.shape[1]
+        lin = torch.from_numpy(np.ascontiguousarray(linear_spec.T)).cuda()[None]
+        return self.out_linear_to_mel_batch(lin, [T])[0].T.double().cpu().numpy()
 
     def trim_silence(self, wav):
         """utils/audio.py:212-217 on the host: drop 0.1 s margins, then librosa 0.6.2
