@@ -22,12 +22,16 @@ sys.path.insert(0, REPO)
 gu = importlib.import_module("your-voice-tts_amd.generic_utils")
 weights = importlib.import_module("your-voice-tts_amd.weights")
 
-EV = ("P1", "B1", "hatt_pub", "B3", "B4", "hdec_pub", "B6", "pre1_pub", "q_pub", "att_A1", "att_A2", "att_ctx_pub")
+# events 8-11: the synthesis form (partials published, partials gathered, A2, none) | the general form
+# (query row published, none, none, context published)
+EV_SYN = ("P1", "B1", "hatt_pub", "B3", "B4", "hdec_pub", "B6", "pre1_pub", "part_pub", "part_gathered", "att_A2", "unused")
+EV_GEN = EV_SYN[:8] + ("q_pub", "unused", "unused", "ctx_pub")
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--L", type=int, default=100)
 ap.add_argument("--nomask", action="store_true", help="Synthesizer.tts()'s configuration (general form)")
 args = ap.parse_args()
+EV = EV_GEN if args.nomask else EV_SYN
 cfg = gu.default_config("config_tacotron2.json")
 cfg.forward_attn_mask = not args.nomask
 m = gu.setup_model(130, cfg, max_batch=1, max_len=256)

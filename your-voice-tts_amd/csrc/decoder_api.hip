@@ -877,9 +877,15 @@ void fill_resident_args(const tts_decoder* d, const RunCtx& c, ResArgs& ra) {
     ra.loc_conv = d->loc_conv_p; ra.loc_dense = d->loc_dense;
     ra.gran = d->gran;
     // first-poll delays (resident.h; round 6: h_att 5 / h_dec 5 took a configs[1] sentence from
-    // 2.65 to 2.29 ms, tools/cases_sleep.txt); TTS_RES_SLEEP_* override them
-    static const int sl_hatt = env_int("TTS_RES_SLEEP_HATT", 5), sl_hdec = env_int("TTS_RES_SLEEP_HDEC", 5),
-                     sl_p1 = env_int("TTS_RES_SLEEP_P1", 0), sl_pre2 = env_int("TTS_RES_SLEEP_PRE2", 2),
+    // 2.65 to 2.29 ms, tools/cases_sleep.txt); TTS_RES_SLEEP_* override them (_Q: the synthesis
+    // form's energy-partials gather and the general form's query gather; _CTX, _E: general form only)
+    // The synthesis form's defaults are h_att 4 / h_dec 3: its CUs issue attention operand loads
+    // ahead of the h_att poll, and the tail / alpha bookkeeping of every CU now sits between the
+    // h_dec publish and its poll (profiles/r10_ab_parts.txt); the general form keeps 5 / 5.
+    static const int sl_hatt_env = env_int("TTS_RES_SLEEP_HATT", -1), sl_hdec_env = env_int("TTS_RES_SLEEP_HDEC", -1);
+    const int sl_hatt = sl_hatt_env >= 0 ? sl_hatt_env : (d->res_gen ? 5 : 4),
+              sl_hdec = sl_hdec_env >= 0 ? sl_hdec_env : (d->res_gen ? 5 : 3);
+    static const int sl_p1 = env_int("TTS_RES_SLEEP_P1", 0), sl_pre2 = env_int("TTS_RES_SLEEP_PRE2", 2),
                      sl_ctx = env_int("TTS_RES_SLEEP_CTX", 0), sl_q = env_int("TTS_RES_SLEEP_Q", 0),
                      sl_e = env_int("TTS_RES_SLEEP_E", 0);
     ra.sleep_hatt = sl_hatt; ra.sleep_hdec = sl_hdec; ra.sleep_p1 = sl_p1; ra.sleep_pre2 = sl_pre2;

@@ -41,10 +41,13 @@ __device__ __forceinline__ void fail(int* status, int code, int step = -1) {
 }
 
 // One wave polls its N granules per lane (idx(i) < 0: none) until every tag equals tag(i);
-// false after `tmo` wall-clock ticks (the caller flags the error, the grid drains).
-template <int N, typename F, typename T>
+// false after `tmo` wall-clock ticks (the caller flags the error, the grid drains).  The clock is
+// read after the first failed poll and then every 32nd; EACH (a wait off every hot path, such as a
+// launch's set-up exchange): read ahead of the first poll and after every failed one, so the
+// bound holds to a poll's length however short `tmo` is.
+template <int N, bool EACH = false, typename F, typename T>
 __device__ __forceinline__ bool sweep2(u64* g, F idx, T tag, float (&v)[N], long long tmo) {
-    long long t_end = 0;
+    long long t_end = EACH ? (long long)wall_clock64() + tmo : 0;
     for (int spin = 0;; ++spin) {
         bool ok = true;
 #pragma unroll
@@ -57,9 +60,9 @@ __device__ __forceinline__ bool sweep2(u64* g, F idx, T tag, float (&v)[N], long
             }
         }
         if (__all(ok)) return true;
-        if (spin == 0) {
+        if (!EACH && spin == 0) {
             t_end = (long long)wall_clock64() + tmo;
-        } else if ((spin & 31) == 0 && (long long)wall_clock64() > t_end) {
+        } else if ((EACH || (spin & 31) == 0) && (long long)wall_clock64() > t_end) {
             return false;
         }
         if (RES_SLEEP) __builtin_amdgcn_s_sleep(RES_SLEEP);
@@ -67,9 +70,9 @@ __device__ __forceinline__ bool sweep2(u64* g, F idx, T tag, float (&v)[N], long
 }
 // One wave polls its N granules per lane (idx(i) < 0: none) until every tag equals `tag`;
 // false after `tmo` wall-clock ticks (the caller flags the error, the grid drains).
-template <int N, typename F>
+template <int N, bool EACH = false, typename F>
 __device__ __forceinline__ bool sweep(u64* g, unsigned tag, float (&v)[N], F idx, long long tmo) {
-    return sweep2<N>(g, idx, [&](int) { return tag; }, v, tmo);
+    return sweep2<N, EACH>(g, idx, [&](int) { return tag; }, v, tmo);
 }
 
 // Granule pairs: every gather of the step loop reads ONE 16-byte pair (2 granules) per lane, an
@@ -102,6 +105,27 @@ __device__ __forceinline__ bool sweep_pair(__amdgpu_buffer_rsrc_t r, int slot, b
         } else if ((spin & 31) == 0 && (long long)wall_clock64() > t_end) {
             return false;
         }
+        if (RES_SLEEP) __builtin_amdgcn_s_sleep(RES_SLEEP);
+    }
+}
+
+// One wave polls one granule per lane at granule slot `slot` (< 0: none) until its tag equals
+// `tag`: the same sc1 buffer load, 8 bytes.  false once `tmo` ticks have passed since the call.
+// The clock is read ahead of the first poll (one scalar load, in flight beside it, consumed only
+// if that poll fails): this gather follows useful work and never spins 32 times, so a timeout
+// counted from the first failed poll and checked every 32nd would not bound it.
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ bool sweep_one(__amdgpu_buffer_rsrc_t r, int slot, unsigned tag, float& v, long long tmo) {
+    const long long t_end = (long long)wall_clock64() + tmo;
+    for (int spin = 0;; ++spin) {
+        bool ok = true;
+        if (slot >= 0) {
+            const u32x2 x = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(r, slot * 8, 0, SC1_VOLATILE));
+            v = __uint_as_float(x.x);
+            ok = x.y == tag;
+        }
+        if (__all(ok)) return true;
+        if ((spin & 31) == 0 && (long long)wall_clock64() > t_end) return false;
         if (RES_SLEEP) __builtin_amdgcn_s_sleep(RES_SLEEP);
     }
 }

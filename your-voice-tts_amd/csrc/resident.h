@@ -3,13 +3,13 @@
 // compute unit) keep every step weight on chip — 16 gate rows of both LSTMs per CU (the
 // attention LSTM's in VGPRs, the decoder LSTM's recurrent/attention half in LDS, its context
 // half in VGPRs) plus a prenet-2 row, a query row and one mel row (LDS).
-// A step then streams no weights from HBM; its cost is the six dependent hand-offs
-//   pre1 -> prenet2 -> h_att -> query -> [attention] -> ctx -> h_dec -> pre1
-// of which pre1, prenet2, query and ctx stay inside one XCD: every XCD computes its own copy of
+// A step then streams no weights from HBM; its cost is the dependent hand-offs
+//   pre1 -> prenet2 -> h_att -> energy partials -> [attention, context] -> h_dec -> pre1
+// (synthesis form, five; the general form has six: ... h_att -> query -> energies -> ctx -> h_dec)
+// of which pre1, prenet2 and the attention's stay inside one XCD: every XCD computes its own copy of
 // the folded prenet-1 rows + stopnet (round 4: those 1.5 MB of rows are read from the XCD's L2
-// every step, prefetched during the context and h_dec gathers; the register file and LDS are full), prenet-2,
-// the query and the attention step (one attention CU per XCD; identical results), so only the
-// two LSTM outputs cross XCDs.  Hand-offs are 8-byte {tag, value} granules (agent-scope relaxed
+// every step, prefetched during the h_dec gather; the register file and LDS are full), prenet-2,
+// the query and the attention step (identical results), so only the two LSTM outputs cross XCDs.  Hand-offs are 8-byte {tag, value} granules (agent-scope relaxed
 // atomics, sc1: the hand-off form that needs no fences, MI355X_MICROARCH.md "Valid forms").
 // Every wait is bounded: a wave that does not see its data within the timeout flags an error
 // and the grid drains.
@@ -17,8 +17,15 @@
 // Scope: B = 1, L <= 256, nmel <= 256 (one mel row per CU; r <= 3), every Tacotron2 attention
 // configuration (common_layers.py:107-256), in two forms:
 //  - the synthesis configuration of synthesize.py:86 (forward attention + eval mask, sigmoid norm,
-//    no location / windowing / transition agent — attention_uses_epart()): one attention CU per XCD
-//    evaluates only the <= 15 positions the mask can keep (resident_decoder_kernel<., false>);
+//    no location / windowing / transition agent — attention_uses_epart()): only the <= 15 positions
+//    the mask can keep are evaluated (resident_decoder_kernel<., false>).  CU rank k of an XCD holds
+//    query rows k + 32 m (m = 0..3), the four dims that lane k of a candidate's 32-lane energy sum
+//    adds up: it forms that lane's partial for the 16 candidate slots and publishes them XCD-locally;
+//    every CU gathers the XCD's 16 x 32 partials (lane = (slot, k)), sums them in that lane order
+//    and finishes the step itself (sigmoid, forward attention + mask, the five weights, all 512
+//    context channels into its own LDS): no query gather, no context hand-off.  Step 0 (and a step
+//    whose candidates all stay below 1e-8) evaluates every position on every CU and exchanges the
+//    whole query for it;
 //  - every other configuration, among them Synthesizer.tts()'s (server/synthesizer.py:46-66 with
 //    config_tacotron2.json: forward attention, sigmoid, mask off) and the constructor default
 //    (location-sensitive + softmax, models/tacotron2.py:17,23): the attention of each XCD is spread
@@ -42,7 +49,9 @@ constexpr int RES_LMAX = 256;
 // granule slots (u64 {tag << 32 | float bits}) per step parity
 // (GR_PRE2X: per-XCD prenet-2 vectors, [8 XCDs][256], written and read inside one XCD; GR_SETUP:
 // each CU's XCD id, parity 0 only)
-// GR_QX: per-XCD query half-rows [8][128 rows][2]; GR_CTXX: per-XCD context + tail [8][528];
+// GR_QX: per-XCD query half-rows [8][128 rows][2] (synthesis form: full-evaluation steps only);
+// GR_CTXX: per-XCD [8][528]: context + tail (general form) | energy partials [16 slots][32 CUs]
+// (synthesis form);
 // GR_P1X: per-XCD prenet-1 rows + continue flag [8][264] (slot 256 = flag).
 // GR_EX: per-XCD attention energies [8][RES_LMAX] (general attention form: each CU of the XCD
 // publishes the energies of its positions, every CU gathers all L).
@@ -120,20 +129,24 @@ struct ResArgs {
     float* stop_hist;
     float* align_hist;
     unsigned long long* gran;  // [2][GR_TOTAL], zeroed before every launch
-    int* status;               // [0]: 0 ok, else the id of the wait that timed out (9: the stop lane's
-                               // own wait for the tail granule, synthesis form)
+    int* status;               // [0]: 0 ok, else the id of the wait that timed out (10: the energy
+                               // partials' gather, synthesis form)
     // s_sleep(4) counts (~0.12 us each) before the first poll of a gather: a poll storm from every CU
-    // slows the hand-off it waits for (device-wide h_att / h_dec; XCD-local pre1, prenet-2, context)
+    // slows the hand-off it waits for (device-wide h_att / h_dec; XCD-local pre1, prenet-2; the
+    // general form's context)
     int sleep_hatt, sleep_hdec, sleep_p1, sleep_pre2, sleep_ctx;
-    int sleep_q, sleep_e;  // s_sleep(1) counts: the query gather, the general form's energy gather
+    // s_sleep(1) counts: the energy partials' gather (synthesis form; its first-poll delay is mostly
+    // the decoder-LSTM half that runs ahead of it) | the general form's query and energy gathers
+    int sleep_q, sleep_e;
     long long* prof;           // null, or RES_PROF_LL: [2][RES_PHASES] wall-clock ticks summed over steps
-                               // per phase (CU 0, attention CU), then the event trace — measurement only
+                               // per phase (CU 0, the alignment-row CU), then the event trace — measurement only
     int prof_marks;            // with prof: also the per-phase marks (they perturb the two CUs that take them)
 };
 constexpr int RES_PHASES = 16;
 // profiling re-run only: prof also holds [256 CU][RES_TRACE_STEPS][RES_TRACE_EV] event ticks
-// (P1, B1, h_att published, B3, B4, h_dec published, B6, pre1 row published, query row published;
-// attention CUs: A1 (query gathered), A2 (candidate energies), context published)
+// (P1, B1, h_att published, B3, B4, h_dec published, B6, pre1 row published; synthesis form: partials
+// published, partials gathered, A2 (candidate energies); general form: query row published [8],
+// context published [11])
 constexpr int RES_TRACE_STEPS = 64, RES_TRACE_EV = 12;
 constexpr size_t RES_PROF_LL = 2 * RES_PHASES + (size_t)RES_CUS * RES_TRACE_STEPS * RES_TRACE_EV;
 

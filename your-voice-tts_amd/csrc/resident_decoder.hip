@@ -5,13 +5,14 @@
 //   1. attention-LSTM partial over [ctx_{t-1} | h_att_{t-1}]            (all waves, VGPR weights)
 //   2. wave 0: wait pre1_t (+ continue flag), prenet-2 row c, publish; gather the 256 rows
 //   3. prenet part, row sums, LSTM cell of units 4c..4c+3, publish h_att_t   (tacotron2.py:195-197)
-//   4. gather h_att_t; 5. CUs < 128: query row c, publish                     (common_layers.py:179)
+//   4. gather h_att_t; 5. four query rows of the XCD's copy (common_layers.py:179); synthesis form:
+//      rows rank + 32 m -> lane `rank`'s partial of the 16 candidate energies, XCD-local publish
 //   6. decoder-LSTM partial over [h_att_t | h_dec_{t-1}]                  (LDS weights)
-//   7. CU 255: energies, sigmoid, forward attention + mask, context, publish ctx_t, then the tail
-//      (common_layers.py:178-182, 199-223, 239-253)
-//   8. gather ctx_t; 9. context part, cell, publish h_dec_t               (tacotron2.py:206-208)
-//  10. gather h_dec_t (the prenet-1 row weights of step 11 in flight from the XCD's L2; the stop
-//      lane's load of the tail granule too: nobody else reads the tail);
+//   7. synthesis form, every CU: gather the XCD's 16 x 32 partials, energies, sigmoid, forward
+//      attention + mask, the five weights, the 512 context channels into its own LDS, the tail
+//      (common_layers.py:178-182, 199-223, 239-253); general form: 7' below, 8. gather ctx_t
+//   9. context part, cell, publish h_dec_t                                (tacotron2.py:206-208)
+//  10. gather h_dec_t (the prenet-1 row weights of step 11 in flight from the XCD's L2);
 //  11. every wave: one folded prenet-1 row of this XCD's copy -> XCD-local publish; the XCD's
 //      stop CU (rank 0), wave 3: the stop row -> sigmoid + stop rule -> XCD-local continue flag
 //      (tacotron2.py:214-224, 256-277).  Mel row c of step t is written by wave 4 during step
@@ -84,6 +85,11 @@ __device__ __forceinline__ int res_candidate(int s, int nn, int np, int L) {
     const int q = p + ((s - 5) & 1);
     return q < L ? q : -1;
 }
+
+// Granule of candidate slot sl's partial from CU rank k, within the XCD's 512 (slot-major: the
+// gathering lane (sl, sub) reads granule tid, a wave four lines; publisher-major [k][sl], one line
+// per publisher and polls strided by 128 bytes, measured 2.2 % slower: DESIGN.md section 10)
+__device__ __forceinline__ int res_part_slot(int sl, int k) { return sl * 32 + k; }
 
 // The eval mask's window of a step whose previous argmax is n (common_layers.py:207-213, Python's
 // negative-index wrap included): position cx = (n-2) mod L takes 0.01 max, positions [clo, chi] =
@@ -176,14 +182,14 @@ __device__ __forceinline__ int res_tail_next(const ResWin& w, float wcx, const f
 
 constexpr int SM_WDL = 16 * 16 * 32 * 4;  // floats of the decoder-LSTM LDS weight image (128 KiB)
 constexpr int SM_ST = 64;                  // biases, cell states, stop-rule state
-constexpr int SM_RQ = 4 * 64 * 4;          // query row [4 i4][64 lanes] float4 | attention CU scratch
-constexpr int SM_RM = 2 * 6 * 64 * 4 + 2 * 256;  // mel row c, stop row: [2][6][64] float4 | row c + energy partials
+constexpr int SM_RQ = 4 * 64 * 4;          // synthesis form: attention scratch | general form: weights, energies
+constexpr int SM_RM = 2 * 6 * 64 * 4 + 2 * 256;  // mel row c, stop row: [2][6][64] float4 | general form: cumulative weights
 constexpr int SM_PROF = 2 * 16;            // RES_PHASES tick accumulators (long long)
 constexpr int SM_FLOATS = SM_WDL + HATT + HDEC + (ENC + 16) + PRE + ADIM + 16 + 16 + SM_ST + SM_RQ + SM_RM + SM_PROF + PRE;
-static_assert(SM_RM >= 6 * 64 * 4 + RES_WAVES * RES_LMAX, "attention CU partials");
-static_assert(SM_RQ >= 3 * RES_LMAX + 2 * RES_WAVES + 16 + ADIM, "attention CU scratch");
+static_assert(SM_RQ >= 3 * RES_LMAX + 2 * RES_WAVES + 16 + ADIM, "synthesis form: attention scratch");
 static_assert(SM_RQ >= 2 * (RES_LMAX + 32) + RES_LMAX + RES_WAVES, "general attention form: weights, energies");
 static_assert(SM_RM >= 2 * 6 * 64 * 4 + RES_LMAX + 32, "general attention form: cumulative weights");
+static_assert(HDEC >= 4 * RES_LMAX, "full evaluation: four waves' partials in xh_dec");
 static_assert(RES_LMAX == 4 * 64 && RES_LMAX == 32 * RES_WAVES, "4 positions per lane, one per wave of 32 CUs");
 
 // PROF: the profiling re-run's instantiation (phase marks, event trace); the production kernel
@@ -208,13 +214,12 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
     float* st = gates + 32;    // [0,16) b_att, [16,32) b_dec (row g*4+u), [32,36) c_att, [36,40) c_dec,
                                // [40,44) h_att, [44,48) h_dec of units 4c+u, [48] mel bias, [49] stop
                                // bias, [50] flag1, [51] count (int bits, stop lane)
-    float* rq = st + SM_ST;    // query row (CUs < 128) | attention CU: aold, an, scr, v
-    float* rm = rq + SM_RQ;    // mel row c, stop row (stop CU) | attention CU: row c + energy partials
+    float* rq = st + SM_ST;    // synthesis form: aold, an, scr, v (every CU)
+    float* rm = rq + SM_RQ;    // mel row c, stop row (stop CU)
     float* abuf = rq;                 // [2][RES_LMAX] previous alpha, ping-pong by step parity
     float* an = abuf + 2 * RES_LMAX;  // unnormalised forward weights of this step
     float* scr = an + RES_LMAX;       // [2 * RES_WAVES] + candidate values [16]
     float* xv = scr + 2 * RES_WAVES + 16;
-    float* red = rm + 6 * 64 * 4;  // [RES_WAVES][RES_LMAX]
     long long* pacc = reinterpret_cast<long long*>(rm + SM_RM);
     float* xp1 = rm + SM_RM + SM_PROF;  // pre1_t (prenet layer 1 output) gathered by wave 0
     // general attention form (every CU): attention weights of the last two steps, zero-padded by
@@ -226,7 +231,7 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
     float* geg = rq + 2 * GW_PAD;       // [RES_LMAX]
     float* gts = geg + RES_LMAX;        // [RES_WAVES]
     float* gcum = rm + 2 * 6 * 64 * 4;  // [GW_PAD]
-    // optional phase timing (thread 0 of CU 0 and of the logging attention CU)
+    // optional phase timing (thread 0 of CU 0 and of the CU that writes the alignment rows)
     bool prof = false;
     long long plast = 0;
     // event trace of the profiling re-run (RES_TRACE_STEPS steps x RES_TRACE_EV events per CU,
@@ -274,6 +279,7 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
     if (tid == 0) {
         flags[0] = 0;
         flags[1] = 0;
+        flags[5] = 0;  // full-evaluation steps so far (synthesis form)
         for (int k = 0; k < RES_PHASES; ++k) pacc[k] = 0;
     }
     __syncthreads();
@@ -288,7 +294,11 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
     if (tid == 0) publish(a.gran + GR_SETUP + c, setup_tag, __int_as_float(xcc));
     if (wave == 0) {
         float v4[4];
-        const bool ok = sweep<4>(a.gran, setup_tag, v4, [&](int i) { return GR_SETUP + lane * 4 + i; }, tmo);
+        // (synthesis form: the strict bound.  Its step waits all follow useful work and none spins
+        // the 32 polls between two clock reads any more, so a timeout shorter than that, such as
+        // the injected one of the fallback test, is met here, where the workgroups' start-up skew
+        // is waited out; the general form keeps its code as it was)
+        const bool ok = sweep<4, !GEN>(a.gran, setup_tag, v4, [&](int i) { return GR_SETUP + lane * 4 + i; }, tmo);
         int rank = 0, nx = 0, nmin = RES_CUS, nmax = 0;
         const int xref = __builtin_amdgcn_readfirstlane(__float_as_int(v4[0]) & 7);  // XCD of CU 0
         for (int k = 0; k < 8; ++k) {
@@ -331,18 +341,19 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
     if (stop_cu && wave == 3)
         for (int i = 0; i < 6; ++i)
             reinterpret_cast<float4*>(rm)[(6 + i) * 64 + lane] = ld4(a.w.wf + (size_t)(a.nmel + PRE) * KF + i * 256 + lane * 4);
-    // query rows 4 rank .. 4 rank + 3 of this XCD's copy: wave w holds half (w & 1) of row 4 rank + w / 2
-    const int qrow = 4 * rank + (wave >> 1), qhalf = wave & 1;
+    // four query rows of this XCD's copy, wave w holds half (w & 1): the general form rows 4 rank + w / 2;
+    // the synthesis form rows rank + 32 (w / 2), the four dims that lane `rank` of a candidate's energy
+    // sum adds up (step 7), so this CU forms that lane's partial of every candidate itself
+    const int qrow = GEN ? 4 * rank + (wave >> 1) : rank + 32 * (wave >> 1), qhalf = wave & 1;
     const float4 wq0 = ld4(a.w.wq + qrow * HATT + qhalf * 512 + lane * 4);
     const float4 wq1 = ld4(a.w.wq + qrow * HATT + qhalf * 512 + 256 + lane * 4);
     const int L = a.L;
-    const bool att_cu = !GEN && rank == nx - 1;       // the last CU of each XCD runs its attention copy
     const bool xlog = xcc == flags[4];                // the XCD whose copies write the outputs
-    const bool att_log = att_cu && xlog;              // ... alignment rows
+    const bool att_log = !GEN && xlog && rank == nx - 1;  // ... alignment rows (synthesis form: one CU of it)
     prof = PROF && a.prof != nullptr && a.prof_marks && (c == 0 || att_log);
     if (prof && tid == 0) plast = (long long)wall_clock64();
     int n = 0, n_prev = 0;
-    float ufa = 0.f, vb = 0.f, ex = 0.f, erow[4] = {0.f, 0.f, 0.f, 0.f}, ptc[4] = {0.f, 0.f, 0.f, 0.f};
+    float ufa = 0.f, vb = 0.f, ex = 0.f, erow[4] = {0.f, 0.f, 0.f, 0.f}, ptc = 0.f;
     // (volatile buffer loads: the compiler may not sink them past the volatile polls of the h_att
     // gather to their use in the context, where their latency would sit on the critical path)
     const auto renc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.enc), (short)0, L * ENC * 4, 0x00020000);
@@ -373,7 +384,7 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
             prefetch_rows(nn);
         }
     };
-    if (att_cu) {
+    if constexpr (!GEN) {  // synthesis form: every CU runs the attention step
         n = a.nidx[0];
         ufa = a.u[0];
         vb = a.v_b[0];
@@ -591,17 +602,18 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         }
         // 4) gather h_att_t (all waves); first wave 4 writes the mel row c of step t-1 (xh_dec, xctx
         //    still hold h_dec_{t-1}, ctx_{t-1}): off the critical path of step t-1's pre1 rows.  The
-        //    attention CU first issues this step's attention operands (the encoder rows the mask can
-        //    keep that it does not hold yet, P at the candidate positions): in flight while h_att is awaited (a load issued
+        //    synthesis form first issues this step's attention operands (the encoder row the mask can
+        //    keep that the CU does not hold yet; wave 0: P of its four dims at the 16 candidate
+        //    positions, one load per lane): in flight while h_att is awaited (a load issued
         //    before the pre1 poll instead held that poll up by its latency, vmcnt being in order, and
         //    with it the XCD's prenet-2 rows: 1.2 us per step, round-4 trace)
-        if (att_cu && t > 0) {
+        if (!GEN && t > 0) {
             advance_rows(n_prev, n);
-            const int pos = res_candidate(tid >> 5, n, n_prev, L);
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-                ptc[m] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-                    rpt, pos >= 0 ? (((tid & 31) + 32 * m) * a.Lcap + pos) * 4 : OOB_OFF, 0, VOLATILE_AUX));
+            if (wave == 0) {  // lane (m = lane / 16, slot = lane % 16): P[rank + 32 m][pos_slot]
+                const int pos = res_candidate(lane & 15, n, n_prev, L);
+                ptc = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+                    rpt, pos >= 0 ? ((rank + 32 * (lane >> 4)) * a.Lcap + pos) * 4 : OOB_OFF, 0, VOLATILE_AUX));
+            }
         }
         {
             if (wave == 4 && t > 0) mel_row(t - 1);
@@ -621,16 +633,41 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
             float s = dot4(wq0, ld4(xh_att + qhalf * 512 + lane * 4), 0.f);
             s = dot4(wq1, ld4(xh_att + qhalf * 512 + 256 + lane * 4), s);
             s = wave_sum_dpp(s);
-            if (lane == 0) publish_xcd(gqs + 2 * qrow + qhalf, E + 3, s);
-            if (tid == 0) { RES_EV(t, 8) }
+            if constexpr (GEN) {
+                if (lane == 0) publish_xcd(gqs + 2 * qrow + qhalf, E + 3, s);
+                if (tid == 0) { RES_EV(t, 8) }
+            } else {
+                // synthesis form: the half-rows stay on this CU (scr[2 w]; a full-evaluation step
+                // publishes them from there, step 7)
+                if (lane == 0) scr[2 * wave] = s;
+            }
         }
-        // 6) decoder LSTM over h_att_t (its h_dec_{t-1} half ran at the loop top).  The attention CU
-        //    too: the query rows are crossing the XCD meanwhile (when this half followed its context
-        //    publish instead, the CU idled here and was then the last to publish h_dec): there as
-        //    two rounds of four chunks whose eight LDS reads are in flight together (left to itself
-        //    the compiler waits for every chunk's pair of reads before the next, eight round trips
-        //    ahead of the attention CU's query gather); the other CUs wait for the context anyway
-        if (att_cu) {
+        if constexpr (!GEN) {
+            // 5') this CU's share of the candidate energies.  Candidate slot sl sums
+            //   part(sub) = sum_m v[sub + 32 m] tanh(q[sub + 32 m] + P[sub + 32 m][pos_sl])   (m = 0..3 in turn)
+            // over sub = 0..31 by a fixed DPP tree (step 7), and part(rank) needs exactly the four query
+            // rows this CU holds: wave 0 forms it for the 16 slots (lane (m, sl) one term, lane sl adds
+            // them in m order) and publishes the 16 partials XCD-locally.  That one edge replaces the
+            // query and the context edge: every CU gathers the XCD's 16 x 32 partials and finishes the
+            // attention step itself.  (Step 0 evaluates every position: nothing to publish.)
+            __syncthreads();  // Q1
+            if (wave == 0 && t > 0) {
+                const int m = lane >> 4;
+                const float q = scr[4 * m] + scr[4 * m + 2];  // half 0 + half 1, as the query gather adds them
+                const float term = __fmul_rn(xv[rank + 32 * m], tanh_fast(__fadd_rn(q, ptc)));
+                const float t1 = __shfl(term, (lane & 15) + 16, 64), t2 = __shfl(term, (lane & 15) + 32, 64),
+                            t3 = __shfl(term, (lane & 15) + 48, 64);
+                const float part = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(0.f, term), t1), t2), t3);
+                if (lane < 16) publish_xcd(gcs + res_part_slot(lane, rank), E + 3, part);
+                if (tid == 0) { RES_EV(t, 8) }
+            }
+        }
+        // 6) decoder LSTM over h_att_t (its h_dec_{t-1} half ran at the loop top).  In the synthesis
+        //    form the energy partials are crossing the XCD meanwhile (useful work that doubles as
+        //    the first-poll delay of their gather): there as two rounds of four chunks whose eight
+        //    LDS reads are in flight together (left to itself the compiler waits for every chunk's
+        //    pair of reads before the next, eight round trips ahead of the gather)
+        if constexpr (!GEN) {
 #pragma unroll 1
             for (int h = 0; h < 8; h += 4) {
                 float4 wv[4], xx[4];
@@ -650,7 +687,6 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         }
         RES_MARK(5);
         float wcx = 0.f, ww[4] = {0.f, 0.f, 0.f, 0.f};  // the step's five weights (ResWin)
-        int n_win = 0;  // attention CU: the n they belong to (alpha and the alignment row follow the h_dec publish)
         // 7) attention step.  After the forward mask the previous alpha is nonzero only on the
         //    previous window S' = W(n') = {(n'-2) mod L} + [n'-1, n'+2], so every position outside
         //    C = W(n) + S' + (S'+1) has mix = 1e-8 exactly and anj = 1e-8 * sigmoid <= 1e-8: the
@@ -829,40 +865,30 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
                 }
             }
         }
-        if (att_cu) {
+        if constexpr (!GEN) {
             const float* aold = abuf + (t & 1) * RES_LMAX;
             float* candv = scr + 2 * RES_WAVES;
             // the window of this step and the forward-attention mix of this thread's candidate: all
-            // of it known before the query arrives
+            // of it known before the partials arrive
             const ResWin win = res_win(n, L);
-            // candidate slot s = tid / 32 (32 lanes x 4 dims): its operands that do not depend on
-            // the query are read before the query arrives
+            // candidate slot s = tid / 32, lane sub = tid % 32 of its energy sum
             const int sl = tid >> 5, sub = tid & 31;
             const int pos = t > 0 ? res_candidate(sl, n, n_prev, L) : -1;
-            float xvd[4];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) xvd[m] = xv[sub + 32 * m];
             const float a_pos = pos >= 0 ? aold[pos] : 0.f, a_prev = pos > 0 ? aold[pos - 1] : 0.f;
             const float mix = __fadd_rn(__fadd_rn(__fmul_rn(1.f - ufa, a_pos), __fmul_rn(ufa, a_prev)), 1e-8f);
             RES_MARK(9);
-            if (wave < 2) {  // query row pk = its two half-rows
-                for (int i = 0; i < a.sleep_q; ++i) __builtin_amdgcn_s_sleep(1);
-                float q0, q1;
-                const bool ok = sweep_pair(rg, s_q + (t & 1) * GR_TOTAL + 2 * pk, true, E + 3, q0, q1, tmo);
-                xq[pk] = q0 + q1;
-                if (!ok && lane == 0) { flags[1] = 1; fail(a.status, 3, t); }
-            }
-            __syncthreads();  // A1
-            if (tid == 0) { RES_EV(t, 9) }
-            if (flags[1]) break;
-            RES_MARK(6);
             bool full = t == 0;
             float rm = -INFINITY;
             float cw[4] = {0.f, 0.f, 0.f, 0.f};  // the window's unnormalised weights an[clo + k]
             if (!full) {
+                // every wave gathers its two slots' 32 partials, one granule per lane: lane (sl, sub)
+                // holds CU sub's partial of slot sl, the lane order of the sum below
+                for (int i = 0; i < a.sleep_q; ++i) __builtin_amdgcn_s_sleep(1);
                 float part = 0.f;
-#pragma unroll
-                for (int m = 0; m < 4; ++m) part += xvd[m] * tanh_fast(xq[sub + 32 * m] + ptc[m]);
+                const bool ok = sweep_one(rg, s_c + (t & 1) * GR_TOTAL + res_part_slot(sl, sub), E + 3, part, tmo);
+                if (!ok && lane == 0) { flags[1] = 1; fail(a.status, 10, t); }
+                if (tid == 0) { RES_EV(t, 9) }
+                RES_MARK(6);
                 const float e = sum32_dpp(part);
                 if (sub == 31) {
                     const float v = pos >= 0 ? __fmul_rn(mix, sigmoid_fast(e + vb)) : -INFINITY;
@@ -871,6 +897,7 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
                 }
                 __syncthreads();  // A2
                 if (tid == 0) { RES_EV(t, 10) }
+                if (flags[1]) break;
                 RES_MARK(14);
                 // one LDS read per lane (slot lane % 16), the max by DPP, the window slots 1-4 (they
                 // hold exactly an[clo + k]: the same lane wrote both) by readlane: no chain of
@@ -882,27 +909,58 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
                 for (int k = 0; k < 4; ++k) cw[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cand), 1 + k));
             }
             if (full) {
-                // every position: wave w owns dims [16w, 16w + 16), lanes own positions
+                // Full evaluation (step 0; a later step whose candidates all stay below 1e-8: rm is
+                // the same on every CU, so the branch is uniform across the grid).  It needs the
+                // whole query on every CU: the half-rows are published and gathered on these steps
+                // only, so their tag counts the full steps (flags[5]) rather than t: a slot's stale
+                // tag is then always an earlier count of this launch, never the awaited one.
+                // (The tests reach this branch at step 0 only: no sentence of the test weights has a
+                // later step below 1e-8, tests/test_gpu_resident_energy_partials.py.  What a later
+                // step adds is read, not run: every read of flags[5] precedes the barrier ahead of
+                // its increment, scr[2 w] still holds this step's half-rows, xh_dec is dead here.)
+                const unsigned F = (a.salt << 14) | (((unsigned)flags[5] & 2047u) << 3) | 3u;
+                if (lane == 0) publish_xcd(gqs + 2 * qrow + qhalf, F, scr[2 * wave]);
+                if (wave < 2) {  // query row pk = its two half-rows
+                    float q0, q1;
+                    const bool ok = sweep_pair(rg, s_q + (t & 1) * GR_TOTAL + 2 * pk, true, F, q0, q1, tmo);
+                    xq[pk] = q0 + q1;
+                    if (!ok && lane == 0) { flags[1] = 1; fail(a.status, 3, t); }
+                }
+                __syncthreads();
+                if (flags[1]) break;
+                if (tid == 0) flags[5] += 1;
+                // every position: wave w owns dims [16w, 16w + 16), lanes own positions.  The wave
+                // partials meet in xh_dec (dead between the mel row of step t-1 and the h_dec gather;
+                // rm's tail holds the stop CU's stop row), four waves at a time, summed in wave order
                 float xqd[16];
 #pragma unroll
                 for (int dd = 0; dd < 16; ++dd) xqd[dd] = xq[16 * wave + dd];
-#pragma unroll 1
-                for (int jj = lane; jj < L; jj += 64) {
-                    float s = 0.f;
-#pragma unroll
-                    for (int dd = 0; dd < 16; ++dd) {
-                        const int d = 16 * wave + dd;
-                        s += xv[d] * tanh_fast(xqd[dd] + a.Pt[(int64_t)d * a.Lcap + jj]);
-                    }
-                    red[wave * RES_LMAX + jj] = s;
-                }
-                __syncthreads();
+                float* red = xh_dec;  // [4][RES_LMAX]
                 const int j = tid;
+                float e = 0.f;
+#pragma unroll 1
+                for (int h = 0; h < 2; ++h) {
+                    if ((wave >> 2) == h) {
+#pragma unroll 1
+                        for (int jj = lane; jj < L; jj += 64) {
+                            float s = 0.f;
+#pragma unroll
+                            for (int dd = 0; dd < 16; ++dd) {
+                                const int d = 16 * wave + dd;
+                                s += xv[d] * tanh_fast(xqd[dd] + a.Pt[(int64_t)d * a.Lcap + jj]);
+                            }
+                            red[(wave & 3) * RES_LMAX + jj] = s;
+                        }
+                    }
+                    __syncthreads();
+                    if (j < L) {
+#pragma unroll
+                        for (int w = 0; w < 4; ++w) e += red[w * RES_LMAX + j];
+                    }
+                    __syncthreads();
+                }
                 float anj = -INFINITY;
                 if (j < L) {
-                    float e = 0.f;
-#pragma unroll
-                    for (int w = 0; w < RES_WAVES; ++w) e += red[w * RES_LMAX + j];
                     const float sg = sigmoid_fast(e + vb);
                     const float prev = j > 0 ? aold[j - 1] : 0.f;
                     const float mixj = __fadd_rn(__fadd_rn(__fmul_rn(1.f - ufa, aold[j]), __fmul_rn(ufa, prev)), 1e-8f);
@@ -919,34 +977,27 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
                 for (int k = 0; k < 4; ++k) cw[k] = an[win.clo + k];
             }
             RES_MARK(7);
-            // straight-line from here to the publish: the five weights, then this thread's channel
+            // straight-line from here to B4: the five weights, then this thread's channel of the
+            // context, into this CU's own LDS (no context hand-off)
             res_weights(win, rm, cw, wcx, ww);
             const float ctx = res_context(win, wcx, ww, ex, erow);
             RES_MARK(15);
-            publish_xcd(gcs + tid, E + 4, ctx);
-            xctx[tid] = ctx;  // this CU skips the gather
-            if (tid == 0) { RES_EV(t, 11) }
-            // off the chain of the 512 channels: the tail (read by the XCD's stop lane alone, in
-            // step 11; rank 0 is never the attention CU) and, after it, the next step's n
-            float tail;
-            const int n_next = res_tail_next(win, wcx, ww, L, tail);
-            if (tid == 0) publish_xcd(gcs + ENC, E + 4, tail);
-            RES_MARK(8);
-            n_win = n;
-            n_prev = n;
-            n = n_next;  // argmax(prev_alpha) of the next step (its loads: h_att wait)
+            xctx[tid] = ctx;  // (the tail and the next step's n follow the h_dec publish)
         }
-        // this wave's prenet-1 row weights (step 11) from the XCD's L2, in flight while the context
-        // (and then h_dec) is awaited
+        // this wave's prenet-1 row weights (step 11) from the XCD's L2: the general form issues them
+        // here, in flight while the context and then h_dec is awaited.  The synthesis form has no
+        // wait ahead of B4, and a barrier waits for the loads issued before it (vmcnt(0): 0.4 us on
+        // the step's chain, measured): it issues them after B5, in flight during the h_dec wait
         float4 w1[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) w1[i] = ld4(w1p + i * 256);
-        // 8) gather ctx_t (waves 0-3: the 512 context values as pairs).  The tail, which the
-        //    attention CU publishes after it, is not waited for here: B4, this CU's cell and its
-        //    h_dec publish need the context only
         if constexpr (GEN) {
-            // (the general form keeps its tail in this gather, wave 4 lane 0: every form of it with
-            // the tail off the gather compiled to more scratch and ran 4 % slower)
+#pragma unroll
+            for (int i = 0; i < 6; ++i) w1[i] = ld4(w1p + i * 256);
+        }
+        // 8) general form: gather ctx_t (waves 0-3: the 512 context values as pairs).  The synthesis
+        //    form has its context in xctx already: B4 only orders those writes
+        if constexpr (GEN) {
+            // (the tail rides in this gather, wave 4 lane 0: every form of it with the tail off the
+            // gather compiled to more scratch and ran 4 % slower)
             if (wave < 5) {
                 const int gc = s_c + (t & 1) * GR_TOTAL;
                 for (int i = 0; i < a.sleep_ctx; ++i) __builtin_amdgcn_s_sleep(4);
@@ -961,19 +1012,11 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
                 }
                 if (!ok && lane == 0) { flags[1] = 1; fail(a.status, 4, t); }
             }
-        } else if (wave < 4 && !att_cu) {
-            const int gc = s_c + (t & 1) * GR_TOTAL;
-            for (int i = 0; i < a.sleep_ctx; ++i) __builtin_amdgcn_s_sleep(4);
-            float c0 = 0.f, c1 = 0.f;
-            const bool ok = sweep_pair(rg, gc + 2 * pk, true, E + 4, c0, c1, tmo);
-            xctx[2 * pk] = c0;
-            xctx[2 * pk + 1] = c1;
-            if (!ok && lane == 0) { flags[1] = 1; fail(a.status, 4, t); }
         }
         __syncthreads();  // B4
         if (tid == 0) { RES_EV(t, 4) }
         if (flags[1]) break;
-        RES_MARK(10);
+        if constexpr (GEN) { RES_MARK(10); }  // (synthesis form: no context wait, the phase reads 0)
         // 9) context part, cell
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc_d = dot4(wdc[i], ld4(xctx + i * 128 + ks * 4), acc_d);
@@ -981,6 +1024,10 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         if (ks == 31) gates[r] = acc_d;
         __syncthreads();  // B5
         RES_MARK(11);
+        if constexpr (!GEN) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) w1[i] = ld4(w1p + i * 256);
+        }
         if (tid < 16) {
             float cs = st[36 + (tid & 3)];
             const float h = lstm_cell16(gates[tid] + st[16 + tid], cs);
@@ -1007,21 +1054,26 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
             }
             if (gf & GEN_LOCATION) gen_location(gw + ((t & 1) ^ 1) * GW_PAD);
         }
-        // the attention CU's alpha (next step's prev_alpha) and alignment row, after its h_dec
-        // publish: the eight attention CUs are the h_dec edge's last publishers
-        if (att_cu) {
+        // synthesis form, after the h_dec publish (off the step's chain: every CU runs the attention
+        // step, so whatever precedes B4 there is on it): the stop rule's tail (read by the stop
+        // lane in step 11) and the next step's n, by one wave (their ~100 selects on all eight
+        // held this CU's h_dec poll up by 0.4 us), handed over in LDS across B6; this step's alpha
+        // (next step's prev_alpha) and, on one CU of the logging XCD, the alignment row
+        if constexpr (!GEN) {
+            const ResWin win = res_win(n, L);
+            if (wave == RES_WAVES - 1) {
+                float tail;
+                const int n_next = res_tail_next(win, wcx, ww, L, tail);
+                if (lane == 0) {
+                    xctx[ENC] = tail;
+                    flags[6] = n_next;
+                }
+            }
             float* anew = abuf + ((t & 1) ^ 1) * RES_LMAX;
-            const float wdef = tid < L ? res_weight_at(res_win(n_win, L), wcx, ww, tid) : 0.f;
+            const float wdef = tid < L ? res_weight_at(win, wcx, ww, tid) : 0.f;
             if (tid < L) anew[tid] = wdef;
             if (att_log && t < a.hist_cap && tid < a.Lalign) a.align_hist[(int64_t)t * a.Lalign + tid] = wdef;
         }
-        // the stop lane's tail granule (tag, value), loaded ahead of the first-poll delay: the
-        // attention CU published it before it reached B4, so step 11 finds it in registers
-        float2 tl = {0.f, 0.f};
-        const int s_tail = s_c + (t & 1) * GR_TOTAL + ENC;
-        if (!GEN && stop_cu && wave == 3)
-            tl = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rg, lane == 0 ? s_tail * 8 : OOB_OFF, 0,
-                                                                                 SC1_VOLATILE));
         // 10) gather h_dec_t
         {
             for (int i = 0; i < a.sleep_hdec; ++i) __builtin_amdgcn_s_sleep(4);
@@ -1034,6 +1086,10 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         __syncthreads();  // B6
         if (tid == 0) { RES_EV(t, 6) }
         if (flags[1]) break;
+        if constexpr (!GEN) {
+            n_prev = n;
+            n = flags[6];  // argmax(prev_alpha) of the next step (its loads: h_att wait)
+        }
         if constexpr (GEN) {
             if (gf & GEN_TA) {
                 float sta = gts[0];
@@ -1078,12 +1134,8 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
                     // every XCD's stop CU decides identically, the logging XCD writes the outputs
                     const float stv = sigmoidf_(ss + st[49]);
                     if (xlog && t < a.hist_cap) a.stop_hist[t] = stv;
-                    // the tail: the early load, or (not yet there) a bounded wait of its own, wait 9
-                    float tail = GEN ? xctx[ENC] : tl.x;
-                    if (!GEN && __float_as_uint(tl.y) != E + 4) {
-                        float unused;
-                        if (!sweep_pair(rg, s_tail, false, E + 4, tail, unused, tmo)) { flags[1] = 1; fail(a.status, 9, t); }
-                    }
+                    // the tail: gathered beside the context (general form), this CU's own (synthesis form)
+                    const float tail = xctx[ENC];
                     int* sst = reinterpret_cast<int*>(st);
                     const int f1 = sst[50] | ((tail > 0.8f && t > L) ? 1 : 0);
                     sst[50] = f1;

@@ -155,6 +155,17 @@ class Tacotron2:
             pass
 
     # ------------------------------------------------------------------ native handles
+    def set_step_cap(self, steps):
+        """``decoder.max_decoder_steps`` for the next runs.  A cap at or below the one the native
+        handles were created for keeps them (``tts_decoder_run`` takes any max_steps <=
+        cfg.max_steps); a larger one re-creates them at the next run, as assigning the attribute
+        does."""
+        steps = int(steps)
+        self.decoder.max_decoder_steps = steps
+        if self._native is not None and steps <= self._native_steps:
+            h, p, key, e = self._native
+            self._native = (h, p, (steps,) + tuple(key[1:]), e)
+
     def _handles(self, Lmax, B, need_steps=0):
         lib = _native.lib()
         if self.device.type != "cuda":
@@ -191,6 +202,7 @@ class Tacotron2:
             _native.check(lib.tts_encoder_create(arr3, len(enc_w), key[2], key[1], stream, ctypes.byref(e)),
                           "tts_encoder_create")
             self._native = (h, p, key, e)
+            self._native_steps = max_steps  # the handles' capacity (set_step_cap)
         return lib, self._native[0], self._native[1]
 
     # ------------------------------------------------------------------ encoder
@@ -444,7 +456,12 @@ class Tacotron2:
 
     def profile_resident_phases(self):
         """Mean µs per decoder step of each phase of the resident batch-1 decoder (last sentence
-        re-run with timers; measurement only): {"cu0": {...}, "attention_cu": {...}}."""
+        re-run with timers; measurement only): {"cu0": {...}, "attention_cu": {...}} (synthesis
+        form: "attention_cu" is the CU that writes the alignment rows; every CU runs the attention
+        step.  There wait_query is the wait of the energy partials' gather, query_dec_early spans
+        the query rows, the partials' publish and the decoder-LSTM half, dec_lstm_hatt the
+        candidate operands read ahead of the gather, and wait_ctx and weights_ctx_publish's publish
+        no longer exist: wait_ctx reads 0, barrier B4 counts into dec_lstm_ctx)."""
         lib, hdec, _ = self._handles(1, 1)
         n = 2 * len(self.RESIDENT_PHASES)
         us = (ctypes.c_float * n)()
@@ -456,8 +473,9 @@ class Tacotron2:
     def profile_resident_trace(self):
         """Per-CU event trace of the last resident sentence, re-run with event stamps only
         (measurement only): int64 numpy [256 CU, 64 steps, 12 events] of wall-clock ticks (P1, B1,
-        h_att published, B3, B4, h_dec published, B6, pre1 row published, query row published;
-        attention CUs: A1, A2, context published; 0 = not reached)."""
+        h_att published, B3, B4, h_dec published, B6, pre1 row published; synthesis form: partials
+        published, partials gathered, A2, unused; general form: query row published, unused,
+        unused, context published; 0 = not reached)."""
         lib, hdec, _ = self._handles(1, 1)
         n = 256 * 64 * 12
         buf = (ctypes.c_longlong * n)()
