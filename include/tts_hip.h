@@ -244,6 +244,43 @@ tts_status tts_gl_draw_phases(tts_gl* g, const int32_t* F, int B, int Fmax, doub
 tts_status tts_gl_save_pcm16(tts_gl* g, const double* wav, int64_t pitch, const int64_t* n, int B, int gap,
                              double peak, int16_t* out, void* stream);
 
+/* AudioProcessor.trim_silence (utils/audio.py:212-217) for a ragged batch on the device: per sentence the
+ * signal is wav[b][margin : N[b] - margin] (n_b samples), and librosa 0.6.2 effects.trim runs on it: reflect
+ * padding by frame_length / 2 (index arithmetic, no padded copy), 1 + n_b / hop_length frames centred on
+ * sample t * hop_length, float64 mean square per frame (one fixed summation order: bitwise run to run),
+ * 10 log10(max(1e-10, .)) against the loudest frame, the frames above -top_db kept.  Relative to the
+ * margin-stripped signal, as the reference's slice: start = first_kept * hop_length, end = min(n_b,
+ * (last_kept + 1) * hop_length); both 0 when no frame is kept.  No sample at or beyond N[b] is read.
+ * INVALID before any launch: a null pointer, B <= 0, N[b] > pitch, N[b] < 2 * margin, a non-positive hop, a
+ * frame length that is not positive and even, and a sentence with n_b < frame_length / 2 + 1 (the padding would need a second reflection;
+ * numpy's pad raises there too): the error text names the sentence.  Waits for the stream before it returns.
+ *   wav [dev] fp64 [B][pitch]; N [host] int32 [B]; start_out, end_out [host] int32 [B] */
+tts_status tts_gl_trim_silence(tts_gl* g, const double* wav, int64_t pitch, const int32_t* N, int B, int margin,
+                               int frame_length, int hop_length, double top_db, int32_t* start_out,
+                               int32_t* end_out, void* stream);
+
+/* AudioProcessor.find_endpoint (utils/audio.py:203-210, the cut of utils/synthesis.py:59-60, 122-123) for a
+ * ragged batch on the device: the candidates are x = k * hop_length, k >= 1, x < N[b] - window_length
+ * (strict, Python's range); the first whose maximum over wav[b][x : x + window_length] is < threshold gives
+ * x + hop_length, and N[b] when there is none.  As in the reference the maximum is of the signed samples
+ * (not of |y|) and the comparison is strict; window_length need not be a multiple of hop_length.  A maximum
+ * rounds nothing: the integers are numpy's.  `threshold` is the caller's 10^(threshold_db * 0.05).
+ * INVALID before any launch: a null pointer, B <= 0, N[b] outside [0, pitch], a non-positive hop or window.
+ * Waits for the stream before it returns.
+ *   wav [dev] fp64 [B][pitch]; N [host] int32 [B]; end_out [host] int32 [B] */
+tts_status tts_gl_find_endpoint(tts_gl* g, const double* wav, int64_t pitch, const int32_t* N, int B,
+                                int window_length, int hop_length, double threshold, int32_t* end_out,
+                                void* stream);
+
+/* The slices the two calls above describe (wav[start:end] of utils/audio.py:217, wav[:end] of
+ * utils/synthesis.py:60), gathered for the analysis entry points: dst[b][0 : len[b]] = src[b][start[b] :
+ * start[b] + len[b]], zeros from len[b] to dst_pitch.  Enqueued on `stream`; does not wait.
+ * INVALID before any launch: a null pointer, B <= 0, a negative start or len, start[b] + len[b] > src_pitch,
+ * len[b] > dst_pitch, dst_pitch < 1.
+ *   src [dev] fp64 [B][src_pitch]; start, len [host] int32 [B]; dst [dev] fp64 [B][dst_pitch] */
+tts_status tts_gl_take_segments(tts_gl* g, const double* src, int64_t src_pitch, const int32_t* start,
+                                const int32_t* len, int B, double* dst, int64_t dst_pitch, void* stream);
+
 /* Mel analysis for GST style wavs: AudioProcessor.melspectrogram (utils/audio.py:146-152) as used by
  * compute_style_mel (utils/synthesis.py:28-35): pre-emphasis FIR, librosa 0.6.2 stft (float64 FFT,
  * complex64 result), |D|, mel projection (float64), amp->dB, _normalize.

@@ -399,8 +399,9 @@ class AudioProcessor:
             return wav[0:0]
         return wav[int(nz[0]) * hop_length:min(len(wav), (int(nz[-1]) + 1) * hop_length)]
 
-    def load_wav(self, filename, sr=None):
-        """utils/audio.py:235-246 with soundfile's float64 conversion (PCM / 2**(bits-1))."""
+    @staticmethod
+    def _read_wav(filename):
+        """(sample rate, float64 samples) of a wav file: soundfile's conversion (PCM / 2**(bits-1))."""
         file_sr, x = scipy.io.wavfile.read(filename)
         if x.dtype == np.int16:
             x = x / 32768.0
@@ -410,10 +411,107 @@ class AudioProcessor:
             x = (x.astype(np.float64) - 128.0) / 128.0
         else:
             x = x.astype(np.float64)
+        return file_sr, x
+
+    def load_wav(self, filename, sr=None):
+        """utils/audio.py:235-246 with soundfile's float64 conversion (PCM / 2**(bits-1))."""
+        file_sr, x = self._read_wav(filename)
         if self.do_trim_silence:
             x = self.trim_silence(x)
         assert self.sample_rate == file_sr, "%s vs %s" % (self.sample_rate, file_sr)
         return x
+
+    # ---------------------------------------------------------------- silence (device)
+    TRIM_TOP_DB, TRIM_FRAME_LENGTH, TRIM_HOP_LENGTH = 40, 1024, 256  # utils/audio.py:216
+
+    def _trim_margin(self):  # utils/audio.py:214
+        return int(self.sample_rate * 0.1)
+
+    def _trim_min_samples(self):
+        """Shortest wav trim_silence_batch takes: the reflect padding of the margin-stripped signal by
+        frame_length / 2 needs frame_length / 2 + 1 samples (np.pad raises ValueError below that)."""
+        return 2 * self._trim_margin() + self.TRIM_FRAME_LENGTH // 2 + 1
+
+    @staticmethod
+    def _wav_batch(wav):
+        assert wav.dim() == 2 and wav.dtype == torch.float64 and wav.is_cuda and wav.stride(1) == 1
+        return wav
+
+    def trim_silence_batch(self, wav, N):
+        """trim_silence of every sentence of the CUDA float64 [B, Nmax] ``wav`` (N: samples per
+        sentence) on the device (tts_gl_trim_silence).  Returns (start, end) as lists, relative to the
+        margin-stripped signals: sentence b trimmed is wav[b, margin + start[b] : margin + end[b]].
+        A sentence shorter than 2 * margin + 513 samples raises."""
+        lib, h = self._handle()
+        wav = self._wav_batch(wav)
+        B = len(N)
+        start, end = (ctypes.c_int32 * B)(), (ctypes.c_int32 * B)()
+        _native.check(lib.tts_gl_trim_silence(h, ctypes.c_void_p(wav.data_ptr()), wav.stride(0), _native.i32_array(N),
+                                              B, self._trim_margin(), self.TRIM_FRAME_LENGTH, self.TRIM_HOP_LENGTH,
+                                              float(self.TRIM_TOP_DB), start, end, _native.stream_handle()),
+                      "tts_gl_trim_silence")
+        return list(start), list(end)
+
+    def find_endpoint_batch(self, wav, N, threshold_db=-40, min_silence_sec=0.8):
+        """find_endpoint of the first N[b] samples of every row of the CUDA float64 [B, Nmax] ``wav`` on
+        the device (tts_gl_find_endpoint); window, hop and threshold as find_endpoint computes them.
+        Returns the list of endpoints."""
+        lib, h = self._handle()
+        wav = self._wav_batch(wav)
+        B = len(N)
+        window_length = int(self.sample_rate * min_silence_sec)
+        hop_length = int(window_length / 4)
+        threshold = float(self._db_to_amp(threshold_db))
+        end = (ctypes.c_int32 * B)()
+        _native.check(lib.tts_gl_find_endpoint(h, ctypes.c_void_p(wav.data_ptr()), wav.stride(0), _native.i32_array(N),
+                                               B, window_length, hop_length, threshold, end,
+                                               _native.stream_handle()), "tts_gl_find_endpoint")
+        return list(end)
+
+    def take_segments(self, wav, start, lens):
+        """wav[b, start[b] : start[b] + lens[b]] of a CUDA float64 [B, pitch] batch as a CUDA float64
+        [B, max(lens)] batch, zeros behind each segment (tts_gl_take_segments)."""
+        lib, h = self._handle()
+        wav = self._wav_batch(wav)
+        B = len(lens)
+        out = torch.empty(B, max(1, max(int(n) for n in lens)), dtype=torch.float64, device=wav.device)
+        _native.check(lib.tts_gl_take_segments(h, ctypes.c_void_p(wav.data_ptr()), wav.stride(0),
+                                               _native.i32_array(start), _native.i32_array(lens), B,
+                                               ctypes.c_void_p(out.data_ptr()), out.stride(0),
+                                               _native.stream_handle()), "tts_gl_take_segments")
+        return out[:, :max(int(n) for n in lens)]
+
+    def load_wav_batch(self, filenames):
+        """load_wav of every file, as one ragged batch on the device: the files are read and converted
+        on the host as load_wav does, uploaded once, and with do_trim_silence trimmed on the device
+        (trim_silence_batch, take_segments).  Returns (CUDA float64 [B, Nmax], samples per sentence),
+        what features_batch / melspectrogram_batch take.  A file too short to trim is kept whole with
+        the reference's message (utils/audio.py:240-244)."""
+        self._handle()  # raises without a GPU / library: no CPU fallback
+        xs = []
+        for filename in filenames:
+            file_sr, x = self._read_wav(filename)
+            assert self.sample_rate == file_sr, "%s vs %s" % (self.sample_rate, file_sr)
+            xs.append(x)
+        N = [len(x) for x in xs]
+        host = np.zeros((len(xs), max(N)), dtype=np.float64)
+        for b, x in enumerate(xs):
+            host[b, :N[b]] = x
+        wav = torch.from_numpy(host).cuda()
+        if not self.do_trim_silence:
+            return wav, N
+        trim = [b for b in range(len(xs)) if N[b] >= self._trim_min_samples()]
+        for b, filename in enumerate(filenames):
+            if b not in trim:
+                print(f' [!] File cannot be trimmed for silence - {filename}')
+        start, lens = [0] * len(xs), list(N)
+        if trim:
+            rows = wav if len(trim) == len(xs) else wav[trim].contiguous()
+            s, e = self.trim_silence_batch(rows, [N[b] for b in trim])
+            margin = self._trim_margin()
+            for i, b in enumerate(trim):
+                start[b], lens[b] = margin + s[i], e[i] - s[i]
+        return self.take_segments(wav, start, lens), lens
 
     def _single(self, spec_nT, mode):
         self._handle()  # raises without a GPU / library: no CPU fallback

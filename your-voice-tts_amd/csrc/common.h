@@ -94,6 +94,15 @@ void mt_work_free(MtWork* w);
 hipError_t pcm16_join(const double* wav, int64_t pitch, const int64_t* start_dev, int64_t total, int B, int gap,
                       double peak, unsigned long long* peak_bits, int16_t* out, hipStream_t s);
 
+// silence.hip: the launches of tts_gl_trim_silence / tts_gl_find_endpoint / tts_gl_take_segments (counts,
+// per-frame values and integer results on the device; the entry points own the buffers and the checks)
+hipError_t silence_trim(const double* wav, int64_t pitch, const int* N_dev, int B, int margin, int frame_length,
+                        int hop, double top_db, double* ms, int Fmax, int* out, hipStream_t s);
+hipError_t silence_endpoint(const double* wav, int64_t pitch, const int* N_dev, int B, int window, int hop,
+                            double threshold, double* wmax, int Kmax, int* out, hipStream_t s);
+hipError_t silence_take_segments(const double* src, int64_t src_pitch, const int* seg, int B, double* dst,
+                                 int64_t dst_pitch, hipStream_t s);
+
 // Persistent kernels (in-launch hand-offs between workgroups: resident decoder / encoder, persistent
 // Griffin-Lim) are only correct if every workgroup of the grid is resident at once.  This checks
 // the grid against the device's occupancy (the kernel's workgroups per CU x CUs, the CU count

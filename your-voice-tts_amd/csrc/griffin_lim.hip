@@ -1980,6 +1980,14 @@ struct tts_gl {
     int64_t* pcm_start = nullptr;
     int pcm_start_n = 0;
     std::vector<int64_t> pcm_start_h;
+    // tts_gl_trim_silence / tts_gl_find_endpoint: one value per frame / candidate window, then the
+    // counts and the integer results ([dev], grown on demand; both calls return with it idle)
+    void* sil = nullptr;
+    size_t sil_n = 0;
+    // tts_gl_take_segments: start / len per sentence ([dev], host copy kept for the upload)
+    int* seg = nullptr;
+    int seg_n = 0;
+    std::vector<int32_t> seg_h;
 };
 
 extern "C" {
@@ -1994,7 +2002,7 @@ void tts_gl_destroy(tts_gl* g) {
     for (void* p : {(void*)g->win, (void*)g->win2, (void*)g->pinv, (void*)g->tw, (void*)g->S, (void*)g->frames,
                     (void*)g->y, (void*)g->F, (void*)g->basis, (void*)g->band, (void*)g->NS, (void*)g->flags, (void*)g->pstatus, (void*)g->pgr, (void*)g->wt, (void*)g->winc,
                     (void*)g->wssp, (void*)g->mt_state, (void*)g->mt_phase, (void*)g->mt_F, (void*)g->pcm_peak,
-                    (void*)g->pcm_start})
+                    (void*)g->pcm_start, g->sil, (void*)g->seg})
         if (p) (void)hipFree(p);
     if (g->host_status) (void)hipHostFree(g->host_status);
     for (hipEvent_t e : {g->ev_in, g->ev_out, g->ev_t0, g->ev_t1, g->ev_done, g->ev_mt})
@@ -2323,6 +2331,122 @@ tts_status tts_gl_save_pcm16(tts_gl* g, const double* wav, int64_t pitch, const 
     TTS_HIP(tts::pcm16_join(wav, pitch, g->pcm_start, g->pcm_start_h[B], B, gap, peak, g->pcm_peak, out, s));
     return TTS_OK;
 }
+}  // extern "C"
+
+namespace tts {
+namespace {
+// the silence workspace: `values` doubles, then `ints` ints (grow only; idle whenever a call begins,
+// since both calls that use it wait for their stream before they return)
+tts_status silence_workspace(tts_gl* g, size_t values, size_t ints, double** v, int** i) {
+    const size_t need = values * sizeof(double) + ints * sizeof(int);
+    if (need > g->sil_n) {
+        if (g->sil) TTS_HIP(hipFree(g->sil));
+        g->sil = nullptr;
+        g->sil_n = 0;
+        TTS_HIP(hipMalloc(&g->sil, need));
+        g->sil_n = need;
+    }
+    *v = static_cast<double*>(g->sil);
+    *i = reinterpret_cast<int*>(*v + values);
+    return TTS_OK;
+}
+}  // namespace
+}  // namespace tts
+
+extern "C" {
+
+tts_status tts_gl_trim_silence(tts_gl* g, const double* wav, int64_t pitch, const int32_t* N, int B, int margin,
+                               int frame_length, int hop_length, double top_db, int32_t* start_out,
+                               int32_t* end_out, void* stream) {
+    TTS_CHECK(g && wav && N && start_out && end_out, TTS_ERR_INVALID, "trim_silence: null argument");
+    TTS_CHECK(B >= 1 && B <= 65535, TTS_ERR_INVALID, "trim_silence: B out of range [1, 65535]");
+    TTS_CHECK(margin >= 0 && frame_length >= 2 && frame_length % 2 == 0 && hop_length >= 1, TTS_ERR_INVALID,
+              "trim_silence: margin must be >= 0, frame_length positive and even, hop_length positive");
+    int Fmax = 1;
+    for (int b = 0; b < B; ++b) {
+        TTS_CHECK(N[b] <= pitch, TTS_ERR_INVALID, "trim_silence: sentence " + std::to_string(b) + " has N[b] > pitch");
+        TTS_CHECK(N[b] >= 2 * (int64_t)margin, TTS_ERR_INVALID,
+                  "trim_silence: sentence " + std::to_string(b) + " is shorter than its two margins");
+        const int n = N[b] - 2 * margin;
+        TTS_CHECK(n >= frame_length / 2 + 1, TTS_ERR_INVALID,
+                  "trim_silence: sentence " + std::to_string(b) + " has " + std::to_string(n) +
+                      " samples between the margins, fewer than frame_length / 2 + 1 = " +
+                      std::to_string(frame_length / 2 + 1) + " (the reflect padding needs one reflection)");
+        Fmax = std::max(Fmax, 1 + n / hop_length);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double* ms;
+    int* iw;  // N [B], start [B], end [B]
+    {
+        tts_status st = tts::silence_workspace(g, (size_t)B * Fmax, (size_t)3 * B, &ms, &iw);
+        if (st) return st;
+    }
+    TTS_HIP(hipMemcpyAsync(iw, N, B * sizeof(int), hipMemcpyHostToDevice, s));
+    TTS_HIP(tts::silence_trim(wav, pitch, iw, B, margin, frame_length, hop_length, top_db, ms, Fmax, iw + B, s));
+    TTS_HIP(hipMemcpyAsync(start_out, iw + B, B * sizeof(int), hipMemcpyDeviceToHost, s));
+    TTS_HIP(hipMemcpyAsync(end_out, iw + 2 * B, B * sizeof(int), hipMemcpyDeviceToHost, s));
+    TTS_HIP(hipStreamSynchronize(s));
+    return TTS_OK;
+}
+
+tts_status tts_gl_find_endpoint(tts_gl* g, const double* wav, int64_t pitch, const int32_t* N, int B,
+                                int window_length, int hop_length, double threshold, int32_t* end_out,
+                                void* stream) {
+    TTS_CHECK(g && wav && N && end_out, TTS_ERR_INVALID, "find_endpoint: null argument");
+    TTS_CHECK(B >= 1 && B <= 65535, TTS_ERR_INVALID, "find_endpoint: B out of range [1, 65535]");
+    TTS_CHECK(window_length >= 1 && hop_length >= 1, TTS_ERR_INVALID,
+              "find_endpoint: window_length and hop_length must be positive");
+    int Kmax = 0;
+    for (int b = 0; b < B; ++b) {
+        TTS_CHECK(N[b] >= 0 && N[b] <= pitch, TTS_ERR_INVALID,
+                  "find_endpoint: sentence " + std::to_string(b) + " has N[b] out of range [0, pitch]");
+        // candidates x = k hop, k >= 1, x < N - window
+        if ((int64_t)N[b] - window_length > hop_length)
+            Kmax = std::max(Kmax, (N[b] - window_length - 1) / hop_length);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double* wmax;
+    int* iw;  // N [B], end [B]
+    {
+        tts_status st = tts::silence_workspace(g, (size_t)B * Kmax, (size_t)2 * B, &wmax, &iw);
+        if (st) return st;
+    }
+    TTS_HIP(hipMemcpyAsync(iw, N, B * sizeof(int), hipMemcpyHostToDevice, s));
+    TTS_HIP(tts::silence_endpoint(wav, pitch, iw, B, window_length, hop_length, threshold, wmax, Kmax, iw + B, s));
+    TTS_HIP(hipMemcpyAsync(end_out, iw + B, B * sizeof(int), hipMemcpyDeviceToHost, s));
+    TTS_HIP(hipStreamSynchronize(s));
+    return TTS_OK;
+}
+
+tts_status tts_gl_take_segments(tts_gl* g, const double* src, int64_t src_pitch, const int32_t* start,
+                                const int32_t* len, int B, double* dst, int64_t dst_pitch, void* stream) {
+    TTS_CHECK(g && src && start && len && dst, TTS_ERR_INVALID, "take_segments: null argument");
+    TTS_CHECK(B >= 1 && B <= 65535, TTS_ERR_INVALID, "take_segments: B out of range [1, 65535]");
+    TTS_CHECK(dst_pitch >= 1 && dst_pitch <= INT32_MAX, TTS_ERR_INVALID, "take_segments: dst_pitch out of range");
+    for (int b = 0; b < B; ++b) {
+        TTS_CHECK(start[b] >= 0 && len[b] >= 0, TTS_ERR_INVALID,
+                  "take_segments: sentence " + std::to_string(b) + " has a negative start or len");
+        TTS_CHECK((int64_t)start[b] + len[b] <= src_pitch, TTS_ERR_INVALID,
+                  "take_segments: sentence " + std::to_string(b) + " has start + len > src_pitch");
+        TTS_CHECK(len[b] <= dst_pitch, TTS_ERR_INVALID,
+                  "take_segments: sentence " + std::to_string(b) + " has len > dst_pitch");
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (2 * B > g->seg_n) {
+        TTS_HIP(hipStreamSynchronize(s));  // (the previous gather on this stream may still read it)
+        if (g->seg) TTS_HIP(hipFree(g->seg));
+        g->seg = nullptr;
+        g->seg_n = 0;
+        TTS_HIP(hipMalloc(&g->seg, 2 * B * sizeof(int)));
+        g->seg_n = 2 * B;
+    }
+    g->seg_h.assign(start, start + B);
+    g->seg_h.insert(g->seg_h.end(), len, len + B);
+    TTS_HIP(hipMemcpyAsync(g->seg, g->seg_h.data(), 2 * B * sizeof(int), hipMemcpyHostToDevice, s));
+    TTS_HIP(tts::silence_take_segments(src, src_pitch, g->seg, B, dst, dst_pitch, s));
+    return TTS_OK;
+}
+
 }  // extern "C"
 
 namespace tts {

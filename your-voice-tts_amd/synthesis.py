@@ -150,14 +150,17 @@ def _decode(model, ids_list, speaker_ids=None):
 
 @torch.no_grad()
 def synthesize_batch(model, ap: AudioProcessor, ids_list, speaker_ids=None, seed=0, phase="device",
-                     iters=None, keep_outputs=False, style_mel=None, to_host=True):
+                     iters=None, keep_outputs=False, style_mel=None, to_host=True, trim_silence=False):
     """ids -> encoder -> HIP decoder -> HIP postnet -> HIP Griffin-Lim for a ragged batch.
 
     phase: "device" draws the initial GL phases on the GPU from ``seed``; "numpy" gives every
     sentence numpy's np.random.rand(1025, T_b) draw in batch order, as the reference does when it
     synthesises the sentences one after another (utils/audio.py:183) -- continued on the device from
     numpy's global state (ap.numpy_phases, phase_mt.hip), which is left where those draws would
-    leave it.  Returns (wavs: list of float64 numpy arrays, or None with to_host=False, info dict;
+    leave it.  trim_silence cuts every waveform at AudioProcessor.find_endpoint as synthesis() does
+    (utils/synthesis.py:59-60, 122-123), found on the device (ap.find_endpoint_batch): info["samples"]
+    then holds the endpoints, and info["wav_dev"] with them feeds ap.pcm16_join as before.
+    Returns (wavs: list of float64 numpy arrays, or None with to_host=False, info dict;
     info["wav_dev"] is the CUDA fp64 [B, N] waveform batch with keep_outputs or to_host=False)."""
     linear = hasattr(model, "linear_dim")  # Tacotron / TacotronGST: linear-spectrogram GL
     if linear:
@@ -175,6 +178,8 @@ def synthesize_batch(model, ap: AudioProcessor, ids_list, speaker_ids=None, seed
     else:
         raise ValueError(f"phase must be 'device' or 'numpy', not {phase!r}")
     lens = [ap.hop_length * (T - 1) for T in frames]
+    if trim_silence:
+        lens = ap.find_endpoint_batch(wav, lens)
     info = dict(frames=frames, steps=out["steps"], samples=lens, decoder_dispatch=out.get("dispatch", "batch"),
                 **model.last_timing, **ap.last_gl_timing())
     if keep_outputs:
