@@ -248,3 +248,47 @@ def test_persistent_griffin_lim_fresh_handles_ignore_freed_granules(audio_cfg):
         assert torch.equal(a, b), k
         del ap
         torch.cuda.synchronize()
+
+
+def test_persistent_griffin_lim_not_placed_with_device_frame_counts(audio_cfg):
+    """tts_synth_run hands Griffin-Lim the decoder's frame counts on the device.  When the persistent
+    launch is then not placed (TTS_CU_CAP), the handle's own count array is staged after all and the
+    initial iSTFT's granules are handed to the fused loop: same waveform and frame count as the
+    multi-launch pipeline, and as the persistent loop of the same handles afterwards.
+    The calls run on a stream of their own: a batch-1 tts_synth_run works on the caller's stream, and
+    the fallbacks' graphs (encoder, Griffin-Lim) cannot be captured on the legacy default stream."""
+    audio = load_pkg("audio")
+    ids = golden("t2_fwdmask_L12")["ids"]
+    m = _t2()
+    ap = audio.AudioProcessor(**{**audio_cfg, "griffin_lim_iters": 4})
+    with torch.cuda.stream(torch.cuda.Stream()):
+        with _env(TTS_CU_CAP=8):
+            wav, frames = m.synthesize_native([ids], ap, seed=1)
+            assert ap.last_gl_path() == "fused"
+        with _env(TTS_RESIDENT=0):
+            ap_ml = audio.AudioProcessor(**{**audio_cfg, "griffin_lim_iters": 4})
+            want, want_frames = _t2().synthesize_native([ids], ap_ml, seed=1)
+        assert list(frames) == list(want_frames) and torch.equal(wav, want)
+        wav = wav.clone()  # (the model's own buffer: the next call reuses it)
+        again, again_frames = m.synthesize_native([ids], ap, seed=1)
+        assert ap.last_gl_path() == "persistent"
+        assert list(again_frames) == list(frames) and torch.equal(again, wav)
+
+
+def test_griffin_lim_graphs_dropped_when_workspace_moves(audio_cfg):
+    """The unfused loop replays a graph per (B, Fmax, iters) that bakes the workspace addresses in.
+    A larger batch moves every buffer: its graph and the first batch's next one are captured anew."""
+    audio = load_pkg("audio")
+    ap = audio.AudioProcessor(**{**audio_cfg, "griffin_lim_iters": 2})
+    rng = np.random.Generator(np.random.PCG64(6))
+    frames = [520, 300, 410]
+    mel = torch.from_numpy(rng.uniform(0, 1, size=(3, 520, 80)).astype(np.float32)).cuda()
+    pu = rng.uniform(0, 1, size=(3, 1025, 520))
+    first = ap.griffin_lim_batch(mel[:2], frames[:2], phase_u=pu[:2])
+    assert ap.last_gl_path() == "unfused"
+    grown = ap.griffin_lim_batch(mel, frames, phase_u=pu)
+    assert ap.last_gl_path() == "unfused"
+    again = ap.griffin_lim_batch(mel[:2], frames[:2], phase_u=pu[:2])
+    assert ap.last_gl_path() == "unfused"
+    assert torch.equal(first, again)
+    assert torch.equal(grown[:2], first)

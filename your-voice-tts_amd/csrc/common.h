@@ -75,33 +75,6 @@ tts_status gl_run_dev(tts_gl* g, int mode, const float* spec, const int32_t* F, 
 tts_status gl_collect(tts_gl* g);  // waits for a pending run, sets its timing, checks its status
 // whether gl_run_dev takes the persistent loop for this shape (host values only)
 bool gl_persistent_path(tts_gl* g, int B, int Fmax, int frames_total, int iters);  // (caches per-F checks in g)
-// phase_mt.hip: numpy's legacy np.random.rand(1025, F[b]) draws for b = 0..B-1 in order, continued
-// on the device from the MT19937 state `state` ([dev] 624 key words + position, updated in place)
-// into out [dev] fp64 [B][1025][Fmax] (F_dev on the device, read on stream s).  The stream is cut into
-// chunks of MT_CHUNK_BLOCKS key blocks, each started by a GF(2) jump-ahead and generated by its own
-// workgroup; `w` holds the caller's device workspace (grown on demand; the caller orders reuse).
-constexpr int MT_MAX_BATCH = 1024;
-struct MtWork {
-    unsigned* xs = nullptr;             // the raw word stream, [blocks][624]
-    size_t xs_words = 0;
-    unsigned long long* polys = nullptr;  // jump polynomials of chunks 1.., [n][312]
-    int npolys = 0;
-    long long* meta = nullptr;          // position, draws, last block, sentence offsets
-};
-hipError_t mt_draw_phases(unsigned* state, const int* F_dev, int B, int Fmax, double* out, MtWork* w, hipStream_t s);
-void mt_work_free(MtWork* w);
-// wav_io.hip: Synthesizer.tts's join + save_wav's int16 conversion (tts_gl_save_pcm16's body)
-hipError_t pcm16_join(const double* wav, int64_t pitch, const int64_t* start_dev, int64_t total, int B, int gap,
-                      double peak, unsigned long long* peak_bits, int16_t* out, hipStream_t s);
-
-// silence.hip: the launches of tts_gl_trim_silence / tts_gl_find_endpoint / tts_gl_take_segments (counts,
-// per-frame values and integer results on the device; the entry points own the buffers and the checks)
-hipError_t silence_trim(const double* wav, int64_t pitch, const int* N_dev, int B, int margin, int frame_length,
-                        int hop, double top_db, double* ms, int Fmax, int* out, hipStream_t s);
-hipError_t silence_endpoint(const double* wav, int64_t pitch, const int* N_dev, int B, int window, int hop,
-                            double threshold, double* wmax, int Kmax, int* out, hipStream_t s);
-hipError_t silence_take_segments(const double* src, int64_t src_pitch, const int* seg, int B, double* dst,
-                                 int64_t dst_pitch, hipStream_t s);
 
 // Persistent kernels (in-launch hand-offs between workgroups: resident decoder / encoder, persistent
 // Griffin-Lim) are only correct if every workgroup of the grid is resident at once.  This checks

@@ -27,12 +27,10 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <map>
-#include <tuple>
 #include <type_traits>
 #include <vector>
 
-#include "common.h"
+#include "gl_fft.h"
 
 #ifndef GLP_SLEEP
 #define GLP_SLEEP 1  // persistent loop: s_sleep between neighbour-tag polls
@@ -42,14 +40,7 @@ using namespace tts;
 
 namespace {
 
-typedef float spec_t;    // |S|^power storage
-typedef float frame_t;   // windowed iSTFT frame storage (every loop: rounded once before librosa's
-                         // float32 overlap-add, which adds each float64 frame into a float32 signal)
-// the persistent loop's frame storage: one 8-byte granule per sample, {tag : 32 | float32 sample},
-// the tag naming the iteration that wrote it (round 4; replaces float64 slots + per-frame flags)
-struct gran_t {
-    unsigned long long v;
-};
+// a frame sample as float64 from its storage (gl_handle.h: frame_t, gran_t), and its store
 __device__ __forceinline__ double fval(float x) { return (double)x; }
 __device__ __forceinline__ double fval(gran_t x) { return (double)__uint_as_float((unsigned)x.v); }
 __device__ __forceinline__ void fstore(float* p, double v, unsigned) { *p = (float)v; }
@@ -57,87 +48,11 @@ __device__ __forceinline__ void fstore(gran_t* p, double v, unsigned tag) {
     p->v = ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint((float)v);
 }
 
-constexpr int NFFT = 2048;
-constexpr int NB = 1025;  // bins
-constexpr int NH = 1024;  // complex FFT size
-constexpr int GL_THREADS = 256;
 constexpr int MAG_KT = 64;  // magnitude kernel tile: bins (one per lane) ...
 constexpr int MAG_FT = 16;  // ... x frames (MAG_FT / 4 per wave)
 constexpr int SCAN_THREADS = 1024;
 constexpr int SCAN_PER = 8;  // samples per thread per scan tile
 constexpr int SCAN_CHUNK = 4096;  // de-emphasis output samples per workgroup
-
-struct Geo {
-    int hop, win, woff, winp;  // woff = (NFFT - win) / 2, winp = win + (woff - fb) rounded up to 4
-    int fb;                    // a frame slot holds samples [fb, fb + winp): fb = woff rounded down to
-                               // even, so sample pairs (2n, 2n+1) are 16-byte aligned
-};
-
-struct GLConst {
-    const double* win;    // [2048] padded periodic Hann
-    const double* win2;   // [2048] win^2
-    const double2* tw;    // [2048] e^{-2 pi i m / 2048}
-};
-
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) {
-    return double2{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x};
-}
-__device__ __forceinline__ double2 cconj(double2 a) { return double2{a.x, -a.y}; }
-
-// Per-thread twiddles of the four twiddled Stockham passes (Ns = 4, 16, 64, 256): loaded once per
-// kernel with the other operands, so the FFT passes wait only on LDS.
-struct FftTw {
-    double2 w[4][3];
-};
-__device__ __forceinline__ FftTw load_fft_tw(const double2* __restrict__ tw) {
-    FftTw t;
-    const int j = threadIdx.x;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int Ns = 4 << (2 * p);
-        const int k = j & (Ns - 1);
-#pragma unroll
-        for (int r = 1; r < 4; ++r) t.w[p][r - 1] = tw[k * r * (512 / Ns)];
-    }
-    return t;
-}
-
-// Stockham radix-4, 5 passes, 256 threads x 1 butterfly.  Returns the buffer holding the result.
-template <bool INV>
-__device__ double2* fft1024(double2* src, double2* dst, const FftTw& tw) {
-    const int j = threadIdx.x;
-#pragma unroll
-    for (int Ns = 1, p = -1; Ns < NH; Ns *= 4, ++p) {
-        const int k = j & (Ns - 1);
-        double2 v[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = src[j + r * 256];
-        if (Ns > 1) {
-#pragma unroll
-            for (int r = 1; r < 4; ++r) {
-                double2 w = tw.w[p][r - 1];
-                if (INV) w = cconj(w);
-                v[r] = cmul(v[r], w);
-            }
-        }
-        const double2 a0 = double2{v[0].x + v[2].x, v[0].y + v[2].y};
-        const double2 a1 = double2{v[0].x - v[2].x, v[0].y - v[2].y};
-        const double2 a2 = double2{v[1].x + v[3].x, v[1].y + v[3].y};
-        const double2 a3 = double2{v[1].x - v[3].x, v[1].y - v[3].y};
-        // -i*a3 = (a3.y, -a3.x); +i*a3 = (-a3.y, a3.x)
-        const double2 m3 = INV ? double2{-a3.y, a3.x} : double2{a3.y, -a3.x};
-        const int idxD = (j / Ns) * Ns * 4 + k;
-        dst[idxD] = double2{a0.x + a2.x, a0.y + a2.y};
-        dst[idxD + Ns] = double2{a1.x + m3.x, a1.y + m3.y};
-        dst[idxD + 2 * Ns] = double2{a0.x - a2.x, a0.y - a2.y};
-        dst[idxD + 3 * Ns] = double2{a1.x - m3.x, a1.y - m3.y};
-        __syncthreads();
-        double2* t = src;
-        src = dst;
-        dst = t;
-    }
-    return src;
-}
 
 // LDS slot of complex point i in the fft1024_regs buffers: rows of 16 points (256 B, all 64
 // banks) with the 16-byte columns XOR-swizzled by 5 * (row mod 4).  The Ns = 1 pass stores lane
@@ -402,15 +317,6 @@ __device__ __forceinline__ int xcd_remap(int bid, int n) {
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
 }
 
-// np.pad(..., mode='reflect') index map for a signal of length N (any overhang).
-__device__ __forceinline__ int reflect_idx(int p, int N) {
-    if ((unsigned)p < (unsigned)N) return p;  // interior: no division
-    if (N == 1) return 0;
-    const int period = 2 * (N - 1);
-    int pp = p % period;
-    if (pp < 0) pp += period;
-    return pp < N ? pp : period - pp;
-}
 
 // float32 y[p] of the previous iteration's iSTFT (librosa istft): float64 frame contributions
 // added frame by frame into a float32 accumulator, divided (float32) by the float32 window
@@ -588,27 +494,6 @@ __global__ __launch_bounds__(256) void gl_magnitude_kernel(const MagArgs a) {
 }
 
 // ---------------------------------------------------------------- GL iteration
-struct IterArgs {
-    const spec_t* S;      // [B][Fmax][1025]
-    const float* y;       // [B][Nmax] the previous iteration's float32 signal (gl_ola_kernel)
-    const void* prev;     // FUSED: the previous iteration's frames (overlap-added here instead)
-    int64_t Nmax;
-    void* next;           // frames written by this iteration (frame_t; gran_t for the initial iSTFT of the persistent loop)
-    const int* F;
-    int Fmax;
-    int B;
-    Geo g;
-    GLConst c;
-    const double* phase_u;  // initial iSTFT only: [B][1025][Fmax] or null (device RNG)
-    unsigned long long seed;
-    unsigned* zero_flags;   // initial iSTFT only: the persistent loop's tag words to clear, or null
-    int* zero_status;       // ... and its status word
-    const double2* wt;      // gl_iter_wave_kernel: [16][4] pass-2 twiddles
-    const double2* winc;    // gl_iter_wave_kernel: [4][64] window cosine seeds (see tts_gl_create)
-    double wrot;            // ... and the recurrence factor 2 cos(2 pi 128 / win)
-    unsigned gtag;          // initial iSTFT into granules (gran_t): the tag of iteration 0
-};
-
 __device__ __forceinline__ double hash_uniform(unsigned long long seed, unsigned long long idx) {
     unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (idx + 1);
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -1500,22 +1385,6 @@ __global__ void gl_gran_to_frames_kernel(const gran_t* in, float* out, int64_t n
 }
 
 // ---------------------------------------------------------------- final OLA + inverse pre-emphasis
-struct FinArgs {
-    const void* frames;  // frame_t (fused / batched loops) or gran_t (persistent): gl_ola_kernel<FT>
-    const int* F;
-    int Fmax, B;
-    Geo g;
-    GLConst c;
-    float* y;  // [B][Nmax]
-    int64_t Nmax;
-    const int* status;  // the persistent loop's status word, or null: nonzero poisons the signal (NaN)
-    int* host_status;   // pinned host word the status is copied to by thread 0 of block (0, 0), or null
-    int* host_seq;      // ... then (pipeline mode) this pinned word is set to `seq` (release), or null
-    int seq;
-    const float* wssp;  // [hop] float32 window sum-square of a sample whose every contributing frame
-                        // exists, by (q - woff) mod hop (summed on the host in ola_sample's order)
-};
-
 template <typename FT>
 __global__ void gl_ola_kernel(const FinArgs a) {
     const int b = blockIdx.y;
@@ -1634,10 +1503,7 @@ bool ola_multi_ok(const Geo& g, int64_t Nmax) {
 }
 // the overlap-add of float32 frames (the fused / batched loops' slots) into the signal
 void launch_ola_frames(const FinArgs& f, hipStream_t s) {
-    static const bool single = [] {  // measurement: TTS_GL_OLA_SINGLE=1, one sample per thread
-        const char* v = getenv("TTS_GL_OLA_SINGLE");
-        return v && v[0] == '1';
-    }();
+    static const bool single = env_is("TTS_GL_OLA_SINGLE", '1');  // measurement: one sample per thread
     if (!single && ola_multi_ok(f.g, f.Nmax))
         hipLaunchKernelGGL(gl_ola_multi_kernel, dim3((unsigned)((f.Nmax + 256 * OLA_R - 1) / (256 * OLA_R)), f.B),
                            dim3(256), 0, s, f);
@@ -1718,427 +1584,18 @@ __global__ __launch_bounds__(SCAN_THREADS) void preemph_scan_kernel(const float*
     }
 }
 
-// ---------------------------------------------------------------- spectrogram / mel analysis
-// AudioProcessor.spectrogram and .melspectrogram (utils/audio.py:138-152) from one STFT, as
-// collate_fn computes them for every wav (datasets/TTSDataset.py:191-192) and compute_style_mel
-// for the GST style wav (utils/synthesis.py:28-35): pre-emphasis FIR (lfilter([1, -c], [1]),
-// :128-131) -> librosa 0.6.2 stft (centre reflect pad, periodic Hann, float64 FFT, complex64
-// result) -> |D| (float32), then
-//   linear: 20 log10(max(min_level, |D|)) - ref_level_db -> _normalize (:79-94)
-//   mel:    mel_basis . |D| (float64) -> the same two steps.
-// One workgroup per (sentence, frame); outputs frame-major [B][Fmax][1025] and [B][Fmax][num_mels]
-// float32, rows at and beyond a sentence's frame count zero.
-struct NormArgs {
-    double min_level, min_db, ref_db, max_norm;
-    int signal_norm, symmetric, clip;
-};
-
-// _amp_to_db(x) - ref_level_db -> _normalize (utils/audio.py:121-123, :79-94), float64
-__device__ __forceinline__ double amp_to_norm_db(double x, const NormArgs& n) {
-    double S = 20.0 * log10(fmax(n.min_level, x)) - n.ref_db;
-    if (n.signal_norm) {
-        S = (S - n.min_db) / -n.min_db;
-        if (n.symmetric) {
-            S = (2.0 * n.max_norm) * S - n.max_norm;
-            if (n.clip) S = fmin(fmax(S, -n.max_norm), n.max_norm);
-        } else {
-            S = n.max_norm * S;
-            if (n.clip) S = fmin(fmax(S, 0.0), n.max_norm);
-        }
-    }
-    return S;
+// one iteration's STFT -> phase -> iSTFT launch in the form a run takes (gl_run_dev's graphs, tts_gl_profile)
+void launch_iteration(bool fused, bool wave, const IterArgs& a, hipStream_t s) {
+    const dim3 grid(a.Fmax, a.B), block(GL_THREADS);
+    if (fused) hipLaunchKernelGGL((gl_iter_kernel<false, true, frame_t>), grid, block, 0, s, a);
+    else if (wave) hipLaunchKernelGGL(gl_iter_wave_kernel<false>, grid, dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((gl_iter_kernel<false, false, frame_t>), grid, block, 0, s, a);
 }
-
-struct MelArgs {
-    const double* wav;  // [B][Nmax]
-    int64_t Nmax;
-    const int* N;       // [B] samples
-    int Fmax;
-    Geo g;
-    GLConst c;
-    const double* basis;  // [num_mels][1025]
-    int n_mels;
-    double coef;          // pre-emphasis (0: none)
-    NormArgs n;
-    float* lin;           // [B][Fmax][1025] (LIN)
-    float* mel;           // [B][Fmax][n_mels] (MEL)
-};
-
-template <bool LIN, bool MEL>
-__global__ __launch_bounds__(GL_THREADS) void analysis_kernel(const MelArgs a) {
-    const int b = blockIdx.y, f = blockIdx.x;
-    const int N = a.N[b];
-    const int F = 1 + N / a.g.hop;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t row = (int64_t)b * a.Fmax + f;
-    if (f >= F) {  // padding row
-        if (LIN)
-            for (int k = tid; k < NB; k += GL_THREADS) a.lin[row * NB + k] = 0.f;
-        if (MEL)
-            for (int m = tid; m < a.n_mels; m += GL_THREADS) a.mel[row * a.n_mels + m] = 0.f;
-        return;
-    }
-    __shared__ __align__(16) double2 buf0[NH];
-    __shared__ __align__(16) double2 buf1[NH];
-    __shared__ float mag[MEL ? NB + 3 : 1];
-    const FftTw ftw = load_fft_tw(a.c.tw);
-    const double* y = a.wav + (int64_t)b * a.Nmax;
-    constexpr int PN = NFFT / GL_THREADS;
-    double* xr = reinterpret_cast<double*>(buf0);
-#pragma unroll
-    for (int i = 0; i < PN; ++i) {
-        const int n = tid + i * GL_THREADS;
-        // np.pad(y_pre, n_fft // 2, mode='reflect') of the pre-emphasised signal
-        const int p = reflect_idx(f * a.g.hop + n - NFFT / 2, N);
-        double v = y[p];
-        if (a.coef != 0.0 && p > 0) v = v - a.coef * y[p - 1];
-        xr[n] = a.c.win[n] * v;
-    }
-    __syncthreads();
-    const double2* Z = fft1024<false>(buf0, buf1, ftw);
-    for (int k = tid; k < NB; k += GL_THREADS) {
-        const double2 zk = Z[k & (NH - 1)];
-        const double2 zc = cconj(Z[(NH - k) & (NH - 1)]);
-        const double2 E = double2{0.5 * (zk.x + zc.x), 0.5 * (zk.y + zc.y)};
-        const double2 O = double2{0.5 * (zk.y - zc.y), -0.5 * (zk.x - zc.x)};
-        const double2 t = a.c.tw[k];
-        const float re = (float)(E.x + (t.x * O.x - t.y * O.y));  // stft result is complex64
-        const float im = (float)(E.y + (t.x * O.y + t.y * O.x));
-        const float mk = hypotf(re, im);  // np.abs on complex64
-        if (MEL) mag[k] = mk;
-        // utils/audio.py:143-144; the float64 min_level promotes the float32 magnitude
-        if (LIN) a.lin[row * NB + k] = (float)amp_to_norm_db((double)mk, a.n);
-    }
-    if (!MEL) return;
-    __syncthreads();
-    // mel bands: each wave owns bands wave, wave+4, ...; lanes stride the 1025 bins, float64
-    for (int m = wave; m < a.n_mels; m += GL_THREADS / 64) {
-        const double* brow = a.basis + (int64_t)m * NB;
-        double acc = 0.0;
-        for (int k = lane; k < NB; k += 64) acc += brow[k] * (double)mag[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-        if (lane == 0) a.mel[row * a.n_mels + m] = (float)amp_to_norm_db(acc, a.n);
-    }
-}
-
-// ---------------------------------------------------------------- linear -> mel
-// AudioProcessor.out_linear_to_mel (utils/audio.py:174-180) on a model's linear output:
-// _denormalize -> + ref_level_db -> 10^(x * 0.05) (float32, as numpy keeps them for a float32
-// input) -> mel_basis . S (float64) -> _amp_to_db - ref_level_db -> _normalize.
-// A workgroup takes L2M_TF consecutive frames of one sentence: their values become amplitudes once,
-// in LDS, and each thread then owns (band, frame) pairs and sums only the band's nonzero bins
-// [band[2m], band[2m+1]) (a Slaney triangle covers a short run of bins; the exact zeros outside it
-// add nothing).  Bins outside [k_lo, k_hi), the union of the bands (above mel_fmax, below mel_fmin),
-// feed no band and are neither read nor converted.  The tile's loads are all issued before the first
-// conversion.  The frame is the fast index of a pair, so a wave's lanes walk bands of similar
-// length, and the rows' odd pitch (1025 floats) spreads the frames over the LDS banks.
-#ifndef TTS_L2M_TF  // frames per workgroup; -DTTS_L2M_TF=n builds the variants of DESIGN 4's sweep (4 won)
-#define TTS_L2M_TF 4
-#endif
-constexpr int L2M_TF = TTS_L2M_TF;
-constexpr int L2M_THREADS = 256;
-constexpr int L2M_PER = (NB + L2M_THREADS - 1) / L2M_THREADS;  // bins of a row per thread
-
-struct L2MArgs {
-    const float* lin;  // [B][Fmax][1025]
-    const int* F;      // [B] frames
-    int Fmax;
-    const double* basis;  // [num_mels][1025]
-    const int* band;      // [num_mels][2]: first nonzero bin, one past the last
-    int k_lo, k_hi;       // the bands' union
-    int n_mels;
-    float min_db, ref_db, max_norm;  // the float32 side (_denormalize, dB -> amplitude)
-    NormArgs n;
-    float* mel;  // [B][Fmax][n_mels]
-};
-
-__global__ __launch_bounds__(L2M_THREADS) void linear_to_mel_kernel(const L2MArgs a) {
-    const int b = blockIdx.y, f0 = blockIdx.x * L2M_TF;
-    const int tid = threadIdx.x;
-    const int F = a.F[b];
-    const int nf = min(L2M_TF, F - f0);              // frames of the sentence in this tile (may be <= 0)
-    const int nt = min(L2M_TF, a.Fmax - f0);         // rows of the tile
-    const int64_t row0 = (int64_t)b * a.Fmax + f0;
-    for (int i = max(nf, 0) * a.n_mels + tid; i < nt * a.n_mels; i += L2M_THREADS) a.mel[row0 * a.n_mels + i] = 0.f;
-    if (nf <= 0) return;
-    __shared__ float amp[L2M_TF * NB];
-    const float* src = a.lin + row0 * NB;
-    float v[L2M_TF][L2M_PER];
-#pragma unroll
-    for (int fl = 0; fl < L2M_TF; ++fl)
-#pragma unroll
-        for (int j = 0; j < L2M_PER; ++j) {
-            const int k = a.k_lo + tid + j * L2M_THREADS;
-            v[fl][j] = fl < nf && k < a.k_hi ? src[fl * NB + k] : 0.f;
-        }
-#pragma unroll
-    for (int fl = 0; fl < L2M_TF; ++fl)
-#pragma unroll
-        for (int j = 0; j < L2M_PER; ++j) {
-            const int k = a.k_lo + tid + j * L2M_THREADS;
-            if (fl >= nf || k >= a.k_hi) continue;
-            float S = v[fl][j];
-            if (a.n.signal_norm) {  // utils/audio.py:96-112
-                if (a.n.symmetric) {
-                    if (a.n.clip) S = fminf(fmaxf(S, -a.max_norm), a.max_norm);
-                    S = ((S + a.max_norm) * -a.min_db / (2.f * a.max_norm)) + a.min_db;
-                } else {
-                    if (a.n.clip) S = fminf(fmaxf(S, 0.f), a.max_norm);
-                    S = (S * -a.min_db / a.max_norm) + a.min_db;
-                }
-            }
-            amp[fl * NB + k] = exp10f((S + a.ref_db) * 0.05f);  // utils/audio.py:176, :125-126
-        }
-    __syncthreads();
-    for (int p = tid; p < a.n_mels * L2M_TF; p += L2M_THREADS) {
-        const int m = p / L2M_TF, fl = p % L2M_TF;
-        if (fl >= nf) continue;
-        const int k0 = a.band[2 * m], k1 = a.band[2 * m + 1];
-        const double* brow = a.basis + (int64_t)m * NB;
-        const float* x = amp + fl * NB;
-        double acc = 0.0;
-#pragma unroll 8  // eight basis loads in flight; the sum keeps its order
-        for (int k = k0; k < k1; ++k) acc += brow[k] * (double)x[k];
-        a.mel[(row0 + fl) * a.n_mels + m] = (float)amp_to_norm_db(acc, a.n);
-    }
-}
-
-bool getenv_off(const char* name) {
-    const char* v = getenv(name);
-    return v && v[0] == '0';
-}
-
-struct GraphKey {
-    int B, Fmax, iters;
-    bool operator<(const GraphKey& o) const { return std::tie(B, Fmax, iters) < std::tie(o.B, o.Fmax, o.iters); }
-};
-
-}  // namespace
-
-struct tts_gl {
-    tts_audio_config cfg{};
-    Geo g{};
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_in = nullptr, ev_out = nullptr, ev_t0 = nullptr, ev_t1 = nullptr;
-    hipEvent_t ev_done = nullptr;  // end of the last tts_gl_run (its status copy included)
-    double *win = nullptr, *win2 = nullptr, *pinv = nullptr, *basis = nullptr;
-    int* NS = nullptr;  // analysis: samples per sentence; linear -> mel: frames per sentence
-    int* band = nullptr;  // [num_mels][2] nonzero bin range of each mel basis row
-    int band_lo = 0, band_hi = 0;  // their union
-    int NS_cap = 0;
-    double2* tw = nullptr;
-    double2* wt = nullptr;  // gl_iter_wave_kernel pass-2 twiddles [16][4]
-    double2* winc = nullptr;  // gl_iter_wave_kernel window rotation bases [4][64]
-    float* wssp = nullptr;    // gl_ola_kernel periodic window sum-square [hop]
-    double wrot = 0.0;
-    bool wave = true;       // batched iterations on gl_iter_wave_kernel (TTS_GL_WAVE=0: gl_iter_kernel)
-    // workspace
-    size_t S_n = 0, fr_n = 0, y_n = 0;
-    spec_t* S = nullptr;
-    void* frames = nullptr;  // frame_t ping-pong slots
-    float* y = nullptr;
-    int* F = nullptr;
-    int Fcap_B = 0;
-    std::map<GraphKey, hipGraphExec_t> graphs;
-    float last_ms = 0.f;
-    int last_launches = 0;
-    bool last_fused = false;
-    bool last_persistent = false;
-    int last_path = TTS_GL_PATH_UNFUSED;
-    unsigned* flags = nullptr;  // persistent loop: [flags_n] the workgroups' XCD table
-    size_t flags_n = 0;
-    gran_t* pgr = nullptr;      // persistent loop: two granule slots
-    size_t pgr_n = 0;
-    std::vector<signed char> gather_fit;  // by frame count: the persistent gather's layout holds (-1: unknown)
-    int* pstatus = nullptr;     // [dev] status of the persistent loop
-    int* host_status = nullptr; // pinned coherent: [0] status of the last persistent loop, [1] its sequence
-    int seq = 0;                // pipeline mode: the sequence the last persistent run's overlap-add sets
-    hipStream_t seq_stream = nullptr;
-    unsigned salt = 0;
-    long long tmo = 0;
-    bool have_last = false;
-    IterArgs last_iter{};
-    bool pipeline = false;        // tts_synth_run: caller's stream, completion collected later
-    bool pending = false;         // a pipeline run whose timing / status is not collected yet
-    bool last_timed = true;       // the last run recorded its events (not in pipeline mode)
-    FinArgs last_fin{};
-    size_t last_fstride = 0;
-    // numpy-stream initial phases (tts_gl_set_phase_state, phase_mt.hip): the MT19937 state on the
-    // device, the phases it drew for the current run, the stream and event of its last draw
-    bool mt_armed = false;
-    unsigned* mt_state = nullptr;  // [625] key + position
-    double* mt_phase = nullptr;    // [B][1025][Fmax]
-    size_t mt_phase_n = 0;
-    int* mt_F = nullptr;           // tts_gl_draw_phases: the frame counts on the device
-    int mt_F_n = 0;
-    hipStream_t mt_stream = nullptr;
-    hipEvent_t ev_mt = nullptr;
-    MtWork mt_work;                // the draws' device workspace (phase_mt.hip)
-    // tts_gl_save_pcm16: the peak word and the output offsets ([dev], host copy kept for the upload)
-    unsigned long long* pcm_peak = nullptr;
-    int64_t* pcm_start = nullptr;
-    int pcm_start_n = 0;
-    std::vector<int64_t> pcm_start_h;
-    // tts_gl_trim_silence / tts_gl_find_endpoint: one value per frame / candidate window, then the
-    // counts and the integer results ([dev], grown on demand; both calls return with it idle)
-    void* sil = nullptr;
-    size_t sil_n = 0;
-    // tts_gl_take_segments: start / len per sentence ([dev], host copy kept for the upload)
-    int* seg = nullptr;
-    int seg_n = 0;
-    std::vector<int32_t> seg_h;
-};
-
-extern "C" {
-
-void tts_gl_destroy(tts_gl* g) {
-    if (!g) return;
-    if (g->stream) (void)hipStreamSynchronize(g->stream);
-    if (g->ev_done) (void)hipEventSynchronize(g->ev_done);  // a pipeline run on another stream
-    if (g->mt_stream) (void)hipEventSynchronize(g->ev_mt);  // the last numpy-stream phase draw
-    mt_work_free(&g->mt_work);
-    for (auto& kv : g->graphs) (void)hipGraphExecDestroy(kv.second);
-    for (void* p : {(void*)g->win, (void*)g->win2, (void*)g->pinv, (void*)g->tw, (void*)g->S, (void*)g->frames,
-                    (void*)g->y, (void*)g->F, (void*)g->basis, (void*)g->band, (void*)g->NS, (void*)g->flags, (void*)g->pstatus, (void*)g->pgr, (void*)g->wt, (void*)g->winc,
-                    (void*)g->wssp, (void*)g->mt_state, (void*)g->mt_phase, (void*)g->mt_F, (void*)g->pcm_peak,
-                    (void*)g->pcm_start, g->sil, (void*)g->seg})
-        if (p) (void)hipFree(p);
-    if (g->host_status) (void)hipHostFree(g->host_status);
-    for (hipEvent_t e : {g->ev_in, g->ev_out, g->ev_t0, g->ev_t1, g->ev_done, g->ev_mt})
-        if (e) (void)hipEventDestroy(e);
-    if (g->stream) (void)hipStreamDestroy(g->stream);
-    delete g;
-}
-
-tts_status tts_gl_create(const tts_audio_config* cfg, const double* inv_mel_basis, void* stream, tts_gl** out) {
-    TTS_CHECK(cfg && out, TTS_ERR_INVALID, "null argument");
-    TTS_CHECK(cfg->n_fft == NFFT, TTS_ERR_UNSUPPORTED, "n_fft must be 2048 (num_freq 1025)");
-    TTS_CHECK(cfg->win_length >= 2 && cfg->win_length <= NFFT, TTS_ERR_INVALID, "win_length must be in [2, n_fft]");
-    TTS_CHECK(cfg->hop_length >= 1 && cfg->hop_length <= cfg->win_length, TTS_ERR_UNSUPPORTED,
-              "hop_length must be in [1, win_length]");
-    TTS_CHECK(cfg->num_mels >= 1 && cfg->num_mels <= 80, TTS_ERR_UNSUPPORTED, "num_mels must be <= 80");
-    auto* g = new tts_gl();
-    g->cfg = *cfg;
-    g->g.hop = cfg->hop_length;
-    g->g.win = cfg->win_length;
-    g->g.woff = (NFFT - cfg->win_length) / 2;  // librosa util.pad_center
-    g->g.fb = g->g.woff & ~1;
-    g->g.winp = (cfg->win_length + (g->g.woff - g->g.fb) + 3) / 4 * 4;
-    (void)stream;
-    std::vector<double> win(NFFT, 0.0), win2(NFFT, 0.0);
-    for (int n = 0; n < cfg->win_length; ++n) {
-        const double w = 0.5 - 0.5 * std::cos(2.0 * M_PI * n / cfg->win_length);  // periodic Hann
-        win[g->g.woff + n] = w;
-        win2[g->g.woff + n] = w * w;
-    }
-    std::vector<double2> tw(NFFT);
-    for (int m = 0; m < NFFT; ++m) tw[m] = double2{std::cos(2.0 * M_PI * m / NFFT), -std::sin(2.0 * M_PI * m / NFFT)};
-    auto fail = [&](hipError_t e, const char* what) {
-        tts_status st = hip_fail(e, what, __FILE__, __LINE__);
-        tts_gl_destroy(g);
-        return st;
-    };
-    hipError_t e;
-    if ((e = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking)) != hipSuccess) return fail(e, "stream");
-    if ((e = hipEventCreateWithFlags(&g->ev_in, hipEventDisableTiming)) != hipSuccess) return fail(e, "event");
-    if ((e = hipEventCreateWithFlags(&g->ev_out, hipEventDisableTiming)) != hipSuccess) return fail(e, "event");
-    if ((e = hipEventCreateWithFlags(&g->ev_done, hipEventDisableTiming)) != hipSuccess) return fail(e, "event");
-    if ((e = hipEventCreateWithFlags(&g->ev_mt, hipEventDisableTiming)) != hipSuccess) return fail(e, "event");
-    if ((e = hipEventCreateWithFlags(&g->ev_t0, hipEventReleaseToDevice)) != hipSuccess) return fail(e, "event");
-    if ((e = hipEventCreateWithFlags(&g->ev_t1, hipEventReleaseToDevice)) != hipSuccess) return fail(e, "event");
-    if ((e = hipMalloc(&g->win, NFFT * 8)) != hipSuccess) return fail(e, "hipMalloc");
-    if ((e = hipMalloc(&g->win2, NFFT * 8)) != hipSuccess) return fail(e, "hipMalloc");
-    if ((e = hipMalloc(&g->tw, NFFT * sizeof(double2))) != hipSuccess) return fail(e, "hipMalloc");
-    if ((e = hipMemcpy(g->win, win.data(), NFFT * 8, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "copy");
-    if ((e = hipMemcpy(g->win2, win2.data(), NFFT * 8, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "copy");
-    if ((e = hipMemcpy(g->tw, tw.data(), NFFT * sizeof(double2), hipMemcpyHostToDevice)) != hipSuccess)
-        return fail(e, "copy");
-    {
-        // wt[q2][p1] = W64^(p1 q2): the pass-2 twiddles of gl_iter_wave_kernel
-        std::vector<double2> wt(64);
-        for (int q2 = 0; q2 < 16; ++q2)
-            for (int p1 = 0; p1 < 4; ++p1) {
-                const double a2 = 2.0 * M_PI * (double)(p1 * q2) / 64.0;
-                wt[q2 * 4 + p1] = double2{std::cos(a2), -std::sin(a2)};
-            }
-        if ((e = hipMalloc(&g->wt, wt.size() * sizeof(double2))) != hipSuccess) return fail(e, "hipMalloc");
-        if ((e = hipMemcpy(g->wt, wt.data(), wt.size() * sizeof(double2), hipMemcpyHostToDevice)) != hipSuccess)
-            return fail(e, "copy");
-        // window cosine seeds (c_0, c_1), c_r = cos(2 pi (s + 128 r - woff) / win), at the first sample
-        // of each lane: input order (s = 2 L + e), output order (s = 2 (16 (L & 3) + (L >> 2)) + e)
-        std::vector<double2> wc(4 * 64);
-        for (int L = 0; L < 64; ++L)
-            for (int e = 0; e < 2; ++e) {
-                const int si = 2 * L + e, so = 2 * (16 * (L & 3) + (L >> 2)) + e;
-                const double ai = 2.0 * M_PI * (double)(si - g->g.woff) / cfg->win_length;
-                const double ao = 2.0 * M_PI * (double)(so - g->g.woff) / cfg->win_length;
-                const double ar = 2.0 * M_PI * 128.0 / cfg->win_length;
-                wc[e * 64 + L] = double2{std::cos(ai), std::cos(ai + ar)};
-                wc[(2 + e) * 64 + L] = double2{std::cos(ao), std::cos(ao + ar)};
-            }
-        g->wrot = 2.0 * std::cos(2.0 * M_PI * 128.0 / cfg->win_length);
-        if ((e = hipMalloc(&g->winc, wc.size() * sizeof(double2))) != hipSuccess) return fail(e, "hipMalloc");
-        if ((e = hipMemcpy(g->winc, wc.data(), wc.size() * sizeof(double2), hipMemcpyHostToDevice)) != hipSuccess)
-            return fail(e, "copy");
-        g->wave = !getenv_off("TTS_GL_WAVE");
-        // window sum-square of a sample q (u = q - woff) with every contributor present: frames
-        // i = ceil((u - win + 1) / hop) .. floor(u / hop) in index order, float32 additions of the
-        // float64 win^2 as ola_sample makes them; depends on u mod hop only
-        const int hop = cfg->hop_length, wl = cfg->win_length;
-        std::vector<float> wp(hop);
-        for (int r = 0; r < hop; ++r) {
-            const int u = r + hop * (wl / hop + 1);
-            const int ilo = (u - wl + 1 + hop - 1) / hop, ihi = u / hop;
-            float w = 0.f;
-            for (int i = ilo; i <= ihi; ++i) w = (float)((double)w + win2[g->g.woff + u - i * hop]);
-            wp[r] = w;
-        }
-        if ((e = hipMalloc(&g->wssp, hop * sizeof(float))) != hipSuccess) return fail(e, "hipMalloc");
-        if ((e = hipMemcpy(g->wssp, wp.data(), hop * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess)
-            return fail(e, "copy");
-    }
-    if (inv_mel_basis) {
-        const size_t n = (size_t)NB * cfg->num_mels;
-        if ((e = hipMalloc(&g->pinv, n * 8)) != hipSuccess) return fail(e, "hipMalloc");
-        std::vector<double> pt(n);
-        for (int k = 0; k < NB; ++k)
-            for (int m = 0; m < cfg->num_mels; ++m) pt[(size_t)m * NB + k] = inv_mel_basis[(size_t)k * cfg->num_mels + m];
-        if ((e = hipMemcpy(g->pinv, pt.data(), n * 8, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "copy");
-    }
-    // persistent GL loop: status word, timeout (50 ms per wait); needs >= 256 compute units
-    {
-        int dev = 0, ncu = 0, rate_khz = 0;
-        if ((e = hipMalloc(&g->pstatus, 16)) != hipSuccess) return fail(e, "hipMalloc");
-        // (an empty speculative run leaves the word as it is: it must start out clean)
-        if ((e = hipMemset(g->pstatus, 0, 16)) != hipSuccess) return fail(e, "hipMemset");
-        if ((e = hipHostMalloc(reinterpret_cast<void**>(&g->host_status), 2 * sizeof(int), hipHostMallocCoherent)) != hipSuccess)
-            return fail(e, "hipHostMalloc");
-        // host_status[1] is polled for ++seq (from 1): a recycled pinned block may hold a stale match
-        g->host_status[0] = 0;
-        g->host_status[1] = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu >= 256 &&
-            hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, dev) == hipSuccess && rate_khz > 0)
-            g->tmo = (long long)rate_khz * 50;
-        // tests only: a tiny per-wait budget forces the timeout path (status, NaN-poisoned signal)
-        const char* tk = getenv("TTS_GL_WAIT_TICKS");
-        if (tk && tk[0] && g->tmo > 0) g->tmo = std::max(1LL, atoll(tk));
-    }
-    *out = g;
-    return TTS_OK;
-}
-
-}  // extern "C"
-
-namespace tts {
-void gl_set_pipeline(tts_gl* g, bool on) { g->pipeline = on; }
 
 // small batches fuse the overlap-add into the iteration launch; at most 256 frames in all run the
 // whole loop as one persistent launch (host values only)
-static bool gl_fused_path(const tts_gl* g, int B, int Fmax) {
-    const char* fz = getenv("TTS_GL_FUSED");
-    return ((int64_t)B * Fmax <= 1024 || (fz && fz[0] == '1')) && (g->g.win + g->g.hop - 1) / g->g.hop <= OLA_MAX;
+bool gl_fused_path(const tts_gl* g, int B, int Fmax) {
+    return ((int64_t)B * Fmax <= 1024 || env_is("TTS_GL_FUSED", '1')) && (g->g.win + g->g.hop - 1) / g->g.hop <= OLA_MAX;
 }
 // The persistent loop overwrites a frame's ping-pong slot once its own contributors have moved on:
 // safe when every reader of a frame is one of its contributors.  Frame f reads the signal at the
@@ -2147,7 +1604,7 @@ static bool gl_fused_path(const tts_gl* g, int B, int Fmax) {
 // suffices (win/2 < hop (F - 1)), R maps the part of W_f outside [0, N) into W_f's own part inside,
 // so R(W_f) = W_f n [0, N) and "f reads fi" <=> W_f n W_fi n [0, N) != {} is symmetric.  Shorter
 // sentences are checked by brute force (host copy of the kernels' index maps).
-static int reflect_host(int p, int N) {
+int reflect_host(int p, int N) {
     if ((unsigned)p < (unsigned)N) return p;
     if (N == 1) return 0;
     const int period = 2 * (N - 1);
@@ -2155,19 +1612,27 @@ static int reflect_host(int p, int N) {
     if (pp < 0) pp += period;
     return pp < N ? pp : period - pp;
 }
-static bool contrib_symmetric(const Geo& g, int F) {
-    if (2 * g.hop * (F - 1) > g.win + 2) return true;
+// The overlap-add contributors of frame f of an F-frame sentence: fn(q, ilo, fi) for every sample
+// of the frame's window (q its reflected, untrimmed position) and every frame fi in ola_sample's
+// range [ilo, ihi] for it.  Stops, and returns false, when fn does.
+template <class Fn>
+bool for_contributors(const Geo& g, int f, int F, Fn fn) {
     const int N = g.hop * (F - 1);
+    for (int n = g.woff; n < g.woff + g.win; ++n) {
+        const int q = reflect_host(f * g.hop + n - NFFT / 2, N) + NFFT / 2;
+        if (q < g.woff) continue;
+        int ilo = q - g.woff - g.win + 1;
+        ilo = ilo <= 0 ? 0 : (ilo + g.hop - 1) / g.hop;
+        const int ihi = std::min((q - g.woff) / g.hop, F - 1);
+        for (int fi = ilo; fi <= ihi; ++fi)
+            if (!fn(q, ilo, fi)) return false;
+    }
+    return true;
+}
+bool contrib_symmetric(const Geo& g, int F) {
     std::vector<char> c((size_t)F * F, 0);
     for (int f = 0; f < F; ++f)
-        for (int n = g.woff; n < g.woff + g.win; ++n) {
-            const int q = reflect_host(f * g.hop + n - NFFT / 2, N) + NFFT / 2;
-            if (q < g.woff) continue;
-            int ilo = q - g.woff - g.win + 1;
-            ilo = ilo <= 0 ? 0 : (ilo + g.hop - 1) / g.hop;
-            const int ihi = std::min((q - g.woff) / g.hop, F - 1);
-            for (int fi = ilo; fi <= ihi; ++fi) c[(size_t)f * F + fi] = 1;
-        }
+        for_contributors(g, f, F, [&](int, int, int fi) { return c[(size_t)f * F + fi] = 1; });
     for (int f = 0; f < F; ++f)
         for (int fi = 0; fi < F; ++fi)
             if (c[(size_t)f * F + fi] != c[(size_t)fi * F + f]) return false;
@@ -2177,7 +1642,7 @@ static bool contrib_symmetric(const Geo& g, int F) {
 // overlap-add contributor within GL_DMAX frames and at most GL_PAIRS granule pairs per thread.  Only
 // frames whose STFT window reaches a sentence edge (reflection) differ from the interior ones: those
 // and one interior frame are checked, restating the kernel's index arithmetic.
-static bool gather_fits(const Geo& g, int F) {
+bool gather_fits(const Geo& g, int F) {
     const int N = g.hop * (F - 1);
     auto frame_ok = [&](int f) {
         int lo[GL_SLOTS], hi[GL_SLOTS];
@@ -2185,19 +1650,14 @@ static bool gather_fits(const Geo& g, int F) {
             lo[k] = 1 << 30;
             hi[k] = -1;
         }
-        for (int n = g.woff; n < g.woff + g.win; ++n) {
-            const int q = reflect_host(f * g.hop + n - NFFT / 2, N) + NFFT / 2;
-            if (q < g.woff) continue;
-            int ilo = q - g.woff - g.win + 1;
-            ilo = ilo <= 0 ? 0 : (ilo + g.hop - 1) / g.hop;
-            const int ihi = std::min((q - g.woff) / g.hop, F - 1);
-            for (int fi = ilo; fi <= ihi; ++fi) {
-                const int sl = fi - f + GL_DMAX;
-                if (sl < 0 || sl >= GL_SLOTS || fi - ilo >= OLA_MAX) return false;
-                lo[sl] = std::min(lo[sl], q - fi * g.hop - g.fb);
-                hi[sl] = std::max(hi[sl], q - fi * g.hop - g.fb);
-            }
-        }
+        const bool near = for_contributors(g, f, F, [&](int q, int ilo, int fi) {
+            const int sl = fi - f + GL_DMAX;
+            if (sl < 0 || sl >= GL_SLOTS || fi - ilo >= OLA_MAX) return false;
+            lo[sl] = std::min(lo[sl], q - fi * g.hop - g.fb);
+            hi[sl] = std::max(hi[sl], q - fi * g.hop - g.fb);
+            return true;
+        });
+        if (!near) return false;
         int pairs = 0;
         for (int k = 0; k < GL_SLOTS; ++k)
             if (hi[k] >= 0) pairs += (hi[k] - (lo[k] & ~1)) / 2 + 1;
@@ -2213,14 +1673,361 @@ static bool gather_fits(const Geo& g, int F) {
     return (g.winp % 2) == 0;
 }
 
+// ---- gl_run_dev: workspace, path, frame counts, phases, the three loops, the final overlap-add ----
+
+// What the stages of one gl_run_dev share; the driver builds it on its stack.
+struct RunCtx {
+    int mode;
+    const float* spec;
+    const int32_t* F;  // host frame counts (upper bounds when F_bound)
+    const int* F_dev;  // the counts on the device, or null
+    bool F_bound;
+    int B, Fmax, iters;
+    const double* phase_u;  // the caller's initial phases, then the numpy-stream draw's, or null
+    uint64_t seed;
+    double* wav;
+    hipStream_t cs, s;  // the caller's stream; the one the run is enqueued on
+    int64_t Nmax;
+    size_t fstride;    // elements of one of the two frame slots
+    int frames_total;
+    bool fused, persistent;  // the path chosen from host values
+    bool persistent_ran;     // ... and whether the persistent launch was placed
+    bool timed;  // loop timers and the completion event (outside pipeline mode)
+    const int* Fd;  // the frame counts the launches read: F_dev, or the handle's own array
+    IterArgs ia;
+    FinArgs fa;
+};
+
+// frame slot i of the two ping-pong slots of the fused / batched loops
+frame_t* frame_slot(const tts_gl* g, const RunCtx& c, int i) { return g->frames.p + (i & 1) * c.fstride; }
+
+// workspace (grow only; graphs bake the buffer addresses and are dropped when they move), then the
+// hand-over from the caller's stream
+tts_status reserve_workspace(tts_gl* g, const RunCtx& c) {
+    const size_t BF = (size_t)c.B * c.Fmax;
+    bool moved = false;
+    // the workspace may move below: nothing of this handle may still be in flight (a pipeline
+    // run's stream has been synchronised by its caller before the next run)
+    if (!g->pipeline) TTS_HIP(hipStreamSynchronize(c.s));
+    TTS_TRY(g->S.reserve(BF * NB, &moved));
+    TTS_TRY(g->frames.reserve(2 * BF * g->g.winp, &moved));
+    TTS_TRY(g->y.reserve((size_t)c.B * c.Nmax, &moved));
+    TTS_TRY(g->F.reserve(c.B, &moved));
+    if (moved) {
+        for (auto& kv : g->graphs) (void)hipGraphExecDestroy(kv.second);
+        g->graphs.clear();
+    }
+    if (c.s != c.cs) {
+        TTS_HIP(hipEventRecord(g->ev_in, c.cs));
+        TTS_HIP(hipStreamWaitEvent(c.s, g->ev_in, 0));
+    }
+    return TTS_OK;
+}
+
+// the handle's own frame-count array from the device counts (a speculative run's host F is only an
+// upper bound: tts_synth_run) or from the host's
+tts_status stage_counts(tts_gl* g, const RunCtx& c) {
+    if (c.F_bound) TTS_HIP(hipMemcpyAsync(g->F.p, c.F_dev, c.B * sizeof(int), hipMemcpyDeviceToDevice, c.s));
+    else TTS_HIP(hipMemcpyAsync(g->F.p, c.F, c.B * sizeof(int), hipMemcpyHostToDevice, c.s));
+    return TTS_OK;
+}
+
+// the reference's np.random.rand draws, continued on the device from numpy's state
+// (tts_gl_set_phase_state): one [1025][F_b] draw per sentence in batch order
+tts_status draw_phases(tts_gl* g, RunCtx& c) {
+    if (c.phase_u || !g->mt_armed) return TTS_OK;
+    const size_t need = (size_t)c.B * NB * c.Fmax;
+    if (need > g->mt_phase.cap && g->mt_stream) TTS_HIP(hipStreamSynchronize(g->mt_stream));  // an earlier run may still read it
+    TTS_TRY(g->mt_phase.reserve(need));
+    TTS_TRY(mt_draw(g, c.Fd, c.B, c.Fmax, g->mt_phase.p, c.s));
+    c.phase_u = g->mt_phase.p;
+    return TTS_OK;
+}
+
+tts_status launch_magnitude(tts_gl* g, const RunCtx& c) {
+    MagArgs ma{};
+    ma.mode = c.mode;
+    ma.spec = c.spec;
+    ma.n_in = c.mode == TTS_GL_FROM_MEL ? g->cfg.num_mels : NB;
+    ma.Fmax = c.Fmax;
+    ma.F = c.Fd;
+    ma.pinv = g->pinv;
+    ma.S = g->S.p;
+    ma.min_db = g->cfg.min_level_db;
+    ma.ref_db = g->cfg.ref_level_db;
+    ma.power = g->cfg.power;
+    ma.max_norm = g->cfg.max_norm;
+    ma.signal_norm = g->cfg.signal_norm;
+    ma.symmetric = g->cfg.symmetric_norm;
+    ma.clip = g->cfg.clip_norm;
+    if (c.mode == TTS_GL_FROM_LINEAR)
+        hipLaunchKernelGGL(gl_linear_magnitude_kernel,
+                           dim3((unsigned)(((int64_t)c.Fmax * NB + 256 * LIN_PER - 1) / (256 * LIN_PER)), c.B), dim3(256), 0,
+                           c.s, ma);
+    else
+        hipLaunchKernelGGL(gl_magnitude_kernel, dim3((NB + MAG_KT - 1) / MAG_KT, (c.Fmax + MAG_FT - 1) / MAG_FT, c.B),
+                           dim3(256), 0, c.s, ma);
+    TTS_HIP(hipGetLastError());
+    return TTS_OK;
+}
+
+// The initial iSTFT into slot 0 (the persistent loop: into tagged granules, with its tag words and
+// status word cleared), the loop's start timer, and the arguments every later launch starts from.
+tts_status launch_init(tts_gl* g, RunCtx& c) {
+    hipStream_t s = c.s;
+    // the persistent loop reads and writes two slots of tagged granules (gl_persistent_kernel);
+    // the other loops two slots of float32 frames (TTS_GL_FUSED=1 forces the fused form at any
+    // batch: measurement knob)
+    if (c.persistent) {
+        bool fresh = false;
+        TTS_TRY(g->pgr.reserve(2 * c.fstride, &fresh));
+        // fresh memory may hold a freed handle's granules, and every handle's salts start at 1: a
+        // stale granule there can carry a tag this handle is about to wait for.  Filled with a word
+        // that is no live tag and not 0 (0 marks an absent contributor: gl_persistent_kernel)
+        if (fresh) TTS_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(g->pgr.p), GL_GRAN_FILL, g->pgr.cap * 2, s));
+        // the initial iSTFT tags its granules with the launch's salt
+        g->salt = (g->salt + 1) & 0x3FFFF;
+        if (g->salt == 0) {
+            // wrapped: a granule of the launch 2^18 back could carry a current tag
+            g->salt = 1;
+            TTS_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(g->pgr.p), GL_GRAN_FILL, g->pgr.cap * 2, s));
+        }
+    }
+    IterArgs& ia = c.ia;
+    ia.S = g->S.p;
+    ia.F = c.Fd;
+    ia.Fmax = c.Fmax;
+    ia.B = c.B;
+    ia.g = g->g;
+    ia.c = GLConst{g->win, g->win2, g->tw};
+    ia.phase_u = c.phase_u;
+    ia.seed = c.seed;
+    ia.y = g->y.p;
+    ia.Nmax = c.Nmax;
+    ia.next = c.persistent ? static_cast<void*>(g->pgr.p) : frame_slot(g, c, 0);
+    ia.wt = g->wt;
+    ia.winc = g->winc;
+    ia.wrot = g->wrot;
+    ia.gtag = g->salt << 14;
+    if (c.persistent) {
+        TTS_TRY(g->flags.reserve((size_t)c.B * c.Fmax));
+        // table entries are salted per launch, and a new handle can get a freed one's words: the
+        // initial iSTFT launch zeroes them and the status word
+        ia.zero_flags = g->flags.p;
+        ia.zero_status = g->pstatus;
+    }
+    const dim3 grid(c.Fmax, c.B), block(GL_THREADS);
+    static const bool wave_init = !env_is("TTS_GL_WAVE_INIT", '0');  // measurement: 0 keeps the block-kernel init
+    if (c.persistent) hipLaunchKernelGGL((gl_iter_kernel<true, false, gran_t>), grid, block, 0, s, ia);
+    else if (!c.fused && g->wave && wave_init)  // the batched loop's own layout for its first launch
+        hipLaunchKernelGGL(gl_iter_wave_kernel<true>, grid, dim3(64), 0, s, ia);
+    else hipLaunchKernelGGL((gl_iter_kernel<true, false, frame_t>), grid, block, 0, s, ia);
+    ia.zero_flags = nullptr;
+    ia.zero_status = nullptr;
+    TTS_HIP(hipGetLastError());
+    // loop timers and the completion event outside pipeline mode only (each event marker holds the
+    // GPU ~5.8 us between the kernels around it); a pipeline run's status travels by sequence word
+    if (c.timed) TTS_HIP(hipEventRecord(g->ev_t0, s));
+    FinArgs& fa = c.fa;
+    fa.F = c.Fd;
+    fa.Fmax = c.Fmax;
+    fa.B = c.B;
+    fa.g = g->g;
+    fa.c = ia.c;
+    fa.y = g->y.p;
+    fa.Nmax = c.Nmax;
+    fa.wssp = g->wssp;
+    return TTS_OK;
+}
+
+// diagnostic (TTS_GL_PHASES): the phase ticks of one frame of the persistent loop, to stderr
+tts_status report_gl_phases(long long* prof, int frame, int iters, hipStream_t s) {
+    long long h[6];
+    TTS_HIP(hipMemcpyAsync(h, prof, sizeof(h), hipMemcpyDeviceToHost, s));
+    TTS_HIP(hipStreamSynchronize(s));
+    TTS_HIP(hipFree(prof));
+    int rate_khz = 100000, dev = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, dev);
+    static const char* names[6] = {"gather", "ola_sums", "fwd_fft", "spectrum", "inv_fft", "store"};
+    fprintf(stderr, "TTS_GL_PHASES frame %d, us per iteration:", frame);
+    for (int k = 0; k < 6; ++k) fprintf(stderr, " %s %.3f", names[k], h[k] * 1e3 / rate_khz / iters);
+    fprintf(stderr, "\n");
+    return TTS_OK;
+}
+
+// The whole loop as one launch.  Every workgroup waits on its neighbours inside it: co-residency
+// guaranteed, or nothing runs (persistent_ran stays false), slot 0 of the granule buffer is handed
+// over as float32 frames and the graph-replayed loop takes the iterations (bitwise the same waveform).
+tts_status run_persistent(tts_gl* g, RunCtx& c) {
+    hipStream_t s = c.s;
+    PersArgs pa{};
+    pa.it = c.ia;
+    pa.frames = g->pgr.p;
+    pa.fstride = (int64_t)c.fstride;
+    pa.iters = c.iters;
+    pa.xtab = g->flags.p;
+    pa.salt = g->salt;
+    pa.tmo = g->tmo;
+    pa.status = g->pstatus;
+    pa.drop_f = -1;
+    if (const char* inj = getenv("TTS_GL_INJECT_DROP"); inj && inj[0]) pa.drop_f = atoi(inj);
+    static const bool gl_nowait = env_is("TTS_GL_NOWAIT", '1');
+    pa.nowait = gl_nowait;
+    // round 6: -19 us per configs[1] sentence (tools/cases_sleep.txt)
+    static const int gl_first_sleep = env_int("TTS_GL_FIRST_SLEEP", 4);
+    pa.first_sleep = gl_first_sleep;
+    long long* prof = nullptr;
+    const char* phases = getenv("TTS_GL_PHASES");
+    if (phases && phases[0]) {  // diagnostic: phase ticks of frame TTS_GL_PHASES (stderr)
+        TTS_HIP(hipMalloc(&prof, 6 * sizeof(long long)));
+        TTS_HIP(hipMemsetAsync(prof, 0, 6 * sizeof(long long), s));
+        pa.prof = prof;
+        pa.prof_f = std::min(atoi(phases), c.frames_total - 1);
+    }
+    void* kargs[] = {&pa};
+    // dynamic LDS: the gather buffer, GL_SLOTS frame slots + the zero word
+    const size_t og_bytes = ((size_t)GL_SLOTS * g->g.winp + 2) * sizeof(float);
+    // up to 256 workgroups: one per compute unit; up to 512: two per compute unit (gl_persistent2_kernel)
+    const dim3 grid(c.Fmax, c.B), block(GL_THREADS);
+    const bool two = (long long)grid.x * grid.y > 256;
+    const void* pfn = two ? reinterpret_cast<const void*>(&gl_persistent2_kernel)
+                          : reinterpret_cast<const void*>(&gl_persistent_kernel);
+    static const hipError_t attr = [] {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gl_persistent_kernel),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gl_persistent2_kernel),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+        return e;
+    }();
+    TTS_HIP(attr);
+    TTS_CHECK(og_bytes <= 96 * 1024, TTS_ERR_INVALID, "persistent Griffin-Lim: window too long for the gather buffer");
+    TTS_HIP(launch_persistent(pfn, grid, block, kargs, og_bytes, s, &c.persistent_ran));
+    if (!c.persistent_ran) {
+        // the initial iSTFT wrote slot 0 of the granule buffer: hand it to the fused loop
+        hipLaunchKernelGGL(gl_gran_to_frames_kernel, dim3((unsigned)((c.fstride + 255) / 256)), dim3(256), 0, s,
+                           g->pgr.p, g->frames.p, (int64_t)c.fstride);
+        TTS_HIP(hipGetLastError());
+        if (prof) {
+            TTS_HIP(hipStreamSynchronize(s));
+            TTS_HIP(hipFree(prof));
+        }
+    } else if (prof) {
+        TTS_TRY(report_gl_phases(prof, pa.prof_f, c.iters, s));
+    }
+    return TTS_OK;
+}
+
+// The iterations as one graph per (B, Fmax, iters), captured on first use.  One iteration =
+// overlap-add of the previous frames into the float32 signal (every sample once) + one workgroup
+// per frame for STFT -> phase -> iSTFT of that signal; the fused form gathers inside that launch.
+tts_status run_graph_loop(tts_gl* g, const RunCtx& c) {
+    hipStream_t s = c.s;
+    GraphKey key{c.B, c.Fmax, c.iters};
+    auto it = g->graphs.find(key);
+    if (it == g->graphs.end()) {
+        hipGraph_t graph = nullptr;
+        TTS_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+        for (int i = 0; i < c.iters; ++i) {
+            IterArgs a = c.ia;
+            a.phase_u = nullptr;
+            a.next = frame_slot(g, c, i + 1);
+            if (c.fused) {
+                a.prev = frame_slot(g, c, i);
+            } else {
+                FinArgs o = c.fa;
+                o.frames = frame_slot(g, c, i);
+                launch_ola_frames(o, s);
+            }
+            launch_iteration(c.fused, g->wave, a, s);
+        }
+        hipError_t ce = hipGetLastError();
+        hipError_t ee = hipStreamEndCapture(s, &graph);
+        TTS_HIP(ce);
+        TTS_HIP(ee);
+        hipGraphExec_t exec = nullptr;
+        TTS_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+        TTS_HIP(hipGraphDestroy(graph));
+        it = g->graphs.emplace(key, exec).first;
+    }
+    TTS_HIP(hipGraphLaunch(it->second, s));
+    return TTS_OK;
+}
+
+// The loop's end timer, the final overlap-add (after a persistent loop: with its status word and,
+// in pipeline mode, the sequence word the host waits for) and the de-emphasis scan into wav.
+tts_status finish(tts_gl* g, RunCtx& c) {
+    hipStream_t s = c.s;
+    FinArgs& fa = c.fa;
+    if (c.timed) TTS_HIP(hipEventRecord(g->ev_t1, s));
+    fa.frames = c.persistent_ran ? static_cast<void*>(g->pgr.p + (size_t)(c.iters & 1) * c.fstride)
+                                 : frame_slot(g, c, c.iters);
+    fa.status = c.persistent_ran ? g->pstatus : nullptr;
+    fa.host_status = c.persistent_ran ? g->host_status : nullptr;  // (no read-back copy launch)
+    if (c.persistent_ran && !c.timed) {
+        fa.host_seq = g->host_status + 1;
+        fa.seq = ++g->seq;
+        g->seq_stream = s;
+    }
+    if (c.persistent_ran)
+        hipLaunchKernelGGL(gl_ola_kernel<gran_t>, dim3((c.Nmax + 255) / 256, c.B), dim3(256), 0, s, fa);
+    else launch_ola_frames(fa, s);
+    fa.status = nullptr;
+    fa.host_status = nullptr;
+    fa.host_seq = nullptr;
+    TTS_HIP(hipGetLastError());
+    // de-emphasis chunks: each starts `look` samples early, |c|^look <= 1e-22; one chunk per
+    // sentence (look 0) when that does not fit one scan tile
+    const double cf = g->cfg.preemphasis, ac = std::fabs(cf);
+    int64_t chunk = SCAN_CHUNK, look = 0;
+    if (ac > 0.0) {
+        const double need = ac < 1.0 ? std::ceil(std::log(1e-22) / std::log(ac)) : 1e30;
+        if (need <= (double)(SCAN_THREADS * SCAN_PER - SCAN_CHUNK - 8)) look = (int64_t)need;
+        else chunk = c.Nmax;
+    }
+    const dim3 sgrid((unsigned)((c.Nmax + chunk - 1) / chunk), c.B);
+    hipLaunchKernelGGL(preemph_scan_kernel, sgrid, dim3(SCAN_THREADS), 0, s, g->y.p, c.Nmax, c.Fd, g->g.hop, cf,
+                       cf != 0.0 ? 1 : 0, chunk, look, c.wav);
+    TTS_HIP(hipGetLastError());
+    return TTS_OK;
+}
+
+// what tts_gl_last_path / tts_gl_last_timing / tts_gl_profile report, the completion event, and
+// (outside pipeline mode) the wait for the run
+tts_status record_last(tts_gl* g, const RunCtx& c) {
+    g->last_persistent = c.persistent_ran;
+    g->last_path = c.persistent_ran ? TTS_GL_PATH_PERSISTENT : c.fused ? TTS_GL_PATH_FUSED : TTS_GL_PATH_UNFUSED;
+    g->last_launches = c.persistent_ran ? 1 : (c.fused ? 1 : 2) * c.iters;
+    if (c.timed) {
+        TTS_HIP(hipEventRecord(g->ev_done, c.s));
+        if (c.s != c.cs) TTS_HIP(hipStreamWaitEvent(c.cs, g->ev_done, 0));
+    } else {
+        g->last_ms = 0.f;  // (pipeline mode: not timed)
+    }
+    g->last_timed = c.timed;
+    g->pending = true;
+    if (!g->pipeline) TTS_TRY(gl_collect(g));
+    g->last_fused = c.fused;
+    g->have_last = true;
+    g->last_iter = c.ia;
+    g->last_fin = c.fa;
+    g->last_fstride = c.fstride;
+    return TTS_OK;
+}
+
+}  // namespace
+
+namespace tts {
+
 bool gl_persistent_path(tts_gl* g, int B, int Fmax, int frames_total, int iters) {
     // (tags hold the iteration in 14 bits below the salt)
     if (!(gl_fused_path(g, B, Fmax) && iters > 0 && iters < (1 << 14) && frames_total <= 512 && g->tmo > 0 &&
-          !getenv_off("TTS_RESIDENT")))
+          !env_is("TTS_RESIDENT", '0')))
         return false;
     // every frame count the run may have (a speculative run knows only the upper bound Fmax)
     for (int F = 2; F <= Fmax; ++F) {
-        if (2 * g->g.hop * (F - 1) > g->g.win + 2) break;  // symmetric from here on (above)
+        if (2 * g->g.hop * (F - 1) > g->g.win + 2) break;  // one reflection suffices: symmetric from here on (above)
         if (!contrib_symmetric(g->g, F)) return false;
     }
     if ((int)g->gather_fit.size() <= Fmax) g->gather_fit.resize(Fmax + 1, -1);
@@ -2229,18 +2036,6 @@ bool gl_persistent_path(tts_gl* g, int B, int Fmax, int frames_total, int iters)
         if (!g->gather_fit[F]) return false;
     }
     return true;
-}
-
-// numpy-stream phases for a run of B sentences (F_dev on the device, read on s) into `out`
-// ([B][1025][Fmax]), continuing the handle's MT19937 state; draws on another stream than the last
-// one wait for it (the stream's order is the draws' order)
-static tts_status mt_draw(tts_gl* g, const int* F_dev, int B, int Fmax, double* out, hipStream_t s) {
-    TTS_CHECK(B <= MT_MAX_BATCH, TTS_ERR_UNSUPPORTED, "numpy-stream phases: at most 1024 sentences per run");
-    if (g->mt_stream && g->mt_stream != s) TTS_HIP(hipStreamWaitEvent(s, g->ev_mt, 0));
-    TTS_HIP(mt_draw_phases(g->mt_state, F_dev, B, Fmax, out, &g->mt_work, s));
-    TTS_HIP(hipEventRecord(g->ev_mt, s));
-    g->mt_stream = s;
-    return TTS_OK;
 }
 
 tts_status gl_collect(tts_gl* g) {
@@ -2257,199 +2052,7 @@ tts_status gl_collect(tts_gl* g) {
         TTS_CHECK(g->host_status[0] == 0, TTS_ERR_HIP, "persistent Griffin-Lim: a hand-off wait timed out (internal error)");
     return TTS_OK;
 }
-}  // namespace tts
 
-extern "C" {
-
-tts_status tts_gl_run(tts_gl* g, int mode, const float* spec, const int32_t* F, int B, int Fmax,
-                      const double* phase_u, uint64_t seed, int iters, double* wav, void* stream) {
-    return tts::gl_run_dev(g, mode, spec, F, nullptr, B, Fmax, phase_u, seed, iters, wav, static_cast<hipStream_t>(stream));
-}
-
-tts_status tts_gl_set_phase_state(tts_gl* g, const uint32_t* key, int pos) {
-    TTS_CHECK(g, TTS_ERR_INVALID, "null handle");
-    if (!key) {
-        g->mt_armed = false;
-        return TTS_OK;
-    }
-    TTS_CHECK(pos >= 0 && pos <= 624, TTS_ERR_INVALID, "MT19937 position must be in [0, 624]");
-    if (!g->mt_state) TTS_HIP(hipMalloc(&g->mt_state, 625 * sizeof(unsigned)));
-    if (g->mt_stream) TTS_HIP(hipEventSynchronize(g->ev_mt));  // a draw may still read the old state
-    unsigned h[625];
-    std::copy(key, key + 624, h);
-    h[624] = (unsigned)pos;
-    TTS_HIP(hipMemcpy(g->mt_state, h, sizeof(h), hipMemcpyHostToDevice));
-    g->mt_armed = true;
-    return TTS_OK;
-}
-
-tts_status tts_gl_get_phase_state(tts_gl* g, uint32_t* key, int* pos) {
-    TTS_CHECK(g && key && pos, TTS_ERR_INVALID, "null argument");
-    TTS_CHECK(g->mt_state, TTS_ERR_INVALID, "no phase state set (tts_gl_set_phase_state)");
-    if (g->mt_stream) TTS_HIP(hipEventSynchronize(g->ev_mt));
-    unsigned h[625];
-    TTS_HIP(hipMemcpy(h, g->mt_state, sizeof(h), hipMemcpyDeviceToHost));
-    std::copy(h, h + 624, key);
-    *pos = (int)h[624];
-    return TTS_OK;
-}
-
-tts_status tts_gl_draw_phases(tts_gl* g, const int32_t* F, int B, int Fmax, double* phase_u, void* stream) {
-    TTS_CHECK(g && F && phase_u && B >= 1 && Fmax >= 1, TTS_ERR_INVALID, "bad draw_phases arguments");
-    TTS_CHECK(g->mt_armed, TTS_ERR_INVALID, "no phase state set (tts_gl_set_phase_state)");
-    for (int b = 0; b < B; ++b) TTS_CHECK(F[b] >= 0 && F[b] <= Fmax, TTS_ERR_INVALID, "F[b] out of range [0, Fmax]");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // (mt_F is rewritten below: a draw on another stream may still read it)
-    if (g->mt_stream && g->mt_stream != s) TTS_HIP(hipStreamWaitEvent(s, g->ev_mt, 0));
-    if (B > g->mt_F_n) {
-        if (g->mt_stream) TTS_HIP(hipEventSynchronize(g->ev_mt));
-        if (g->mt_F) TTS_HIP(hipFree(g->mt_F));
-        g->mt_F = nullptr;
-        TTS_HIP(hipMalloc(&g->mt_F, B * sizeof(int)));
-        g->mt_F_n = B;
-    }
-    TTS_HIP(hipMemcpyAsync(g->mt_F, F, B * sizeof(int), hipMemcpyHostToDevice, s));
-    return tts::mt_draw(g, g->mt_F, B, Fmax, phase_u, s);
-}
-
-tts_status tts_gl_save_pcm16(tts_gl* g, const double* wav, int64_t pitch, const int64_t* n, int B, int gap,
-                             double peak, int16_t* out, void* stream) {
-    TTS_CHECK(g && wav && n && out && B >= 1 && gap >= 0, TTS_ERR_INVALID, "bad save_pcm16 arguments");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    for (int b = 0; b < B; ++b) TTS_CHECK(n[b] >= 0 && n[b] <= pitch, TTS_ERR_INVALID, "n[b] out of range [0, pitch]");
-    if (!g->pcm_peak) TTS_HIP(hipMalloc(&g->pcm_peak, sizeof(unsigned long long)));
-    if (B + 1 > g->pcm_start_n) {
-        TTS_HIP(hipStreamSynchronize(s));  // (the previous join on this stream may still read it)
-        if (g->pcm_start) TTS_HIP(hipFree(g->pcm_start));
-        g->pcm_start = nullptr;
-        TTS_HIP(hipMalloc(&g->pcm_start, (B + 1) * sizeof(int64_t)));
-        g->pcm_start_n = B + 1;
-    }
-    g->pcm_start_h.assign(B + 1, 0);
-    for (int b = 0; b < B; ++b) g->pcm_start_h[b + 1] = g->pcm_start_h[b] + n[b] + gap;
-    TTS_HIP(hipMemcpyAsync(g->pcm_start, g->pcm_start_h.data(), (B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    TTS_HIP(tts::pcm16_join(wav, pitch, g->pcm_start, g->pcm_start_h[B], B, gap, peak, g->pcm_peak, out, s));
-    return TTS_OK;
-}
-}  // extern "C"
-
-namespace tts {
-namespace {
-// the silence workspace: `values` doubles, then `ints` ints (grow only; idle whenever a call begins,
-// since both calls that use it wait for their stream before they return)
-tts_status silence_workspace(tts_gl* g, size_t values, size_t ints, double** v, int** i) {
-    const size_t need = values * sizeof(double) + ints * sizeof(int);
-    if (need > g->sil_n) {
-        if (g->sil) TTS_HIP(hipFree(g->sil));
-        g->sil = nullptr;
-        g->sil_n = 0;
-        TTS_HIP(hipMalloc(&g->sil, need));
-        g->sil_n = need;
-    }
-    *v = static_cast<double*>(g->sil);
-    *i = reinterpret_cast<int*>(*v + values);
-    return TTS_OK;
-}
-}  // namespace
-}  // namespace tts
-
-extern "C" {
-
-tts_status tts_gl_trim_silence(tts_gl* g, const double* wav, int64_t pitch, const int32_t* N, int B, int margin,
-                               int frame_length, int hop_length, double top_db, int32_t* start_out,
-                               int32_t* end_out, void* stream) {
-    TTS_CHECK(g && wav && N && start_out && end_out, TTS_ERR_INVALID, "trim_silence: null argument");
-    TTS_CHECK(B >= 1 && B <= 65535, TTS_ERR_INVALID, "trim_silence: B out of range [1, 65535]");
-    TTS_CHECK(margin >= 0 && frame_length >= 2 && frame_length % 2 == 0 && hop_length >= 1, TTS_ERR_INVALID,
-              "trim_silence: margin must be >= 0, frame_length positive and even, hop_length positive");
-    int Fmax = 1;
-    for (int b = 0; b < B; ++b) {
-        TTS_CHECK(N[b] <= pitch, TTS_ERR_INVALID, "trim_silence: sentence " + std::to_string(b) + " has N[b] > pitch");
-        TTS_CHECK(N[b] >= 2 * (int64_t)margin, TTS_ERR_INVALID,
-                  "trim_silence: sentence " + std::to_string(b) + " is shorter than its two margins");
-        const int n = N[b] - 2 * margin;
-        TTS_CHECK(n >= frame_length / 2 + 1, TTS_ERR_INVALID,
-                  "trim_silence: sentence " + std::to_string(b) + " has " + std::to_string(n) +
-                      " samples between the margins, fewer than frame_length / 2 + 1 = " +
-                      std::to_string(frame_length / 2 + 1) + " (the reflect padding needs one reflection)");
-        Fmax = std::max(Fmax, 1 + n / hop_length);
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    double* ms;
-    int* iw;  // N [B], start [B], end [B]
-    {
-        tts_status st = tts::silence_workspace(g, (size_t)B * Fmax, (size_t)3 * B, &ms, &iw);
-        if (st) return st;
-    }
-    TTS_HIP(hipMemcpyAsync(iw, N, B * sizeof(int), hipMemcpyHostToDevice, s));
-    TTS_HIP(tts::silence_trim(wav, pitch, iw, B, margin, frame_length, hop_length, top_db, ms, Fmax, iw + B, s));
-    TTS_HIP(hipMemcpyAsync(start_out, iw + B, B * sizeof(int), hipMemcpyDeviceToHost, s));
-    TTS_HIP(hipMemcpyAsync(end_out, iw + 2 * B, B * sizeof(int), hipMemcpyDeviceToHost, s));
-    TTS_HIP(hipStreamSynchronize(s));
-    return TTS_OK;
-}
-
-tts_status tts_gl_find_endpoint(tts_gl* g, const double* wav, int64_t pitch, const int32_t* N, int B,
-                                int window_length, int hop_length, double threshold, int32_t* end_out,
-                                void* stream) {
-    TTS_CHECK(g && wav && N && end_out, TTS_ERR_INVALID, "find_endpoint: null argument");
-    TTS_CHECK(B >= 1 && B <= 65535, TTS_ERR_INVALID, "find_endpoint: B out of range [1, 65535]");
-    TTS_CHECK(window_length >= 1 && hop_length >= 1, TTS_ERR_INVALID,
-              "find_endpoint: window_length and hop_length must be positive");
-    int Kmax = 0;
-    for (int b = 0; b < B; ++b) {
-        TTS_CHECK(N[b] >= 0 && N[b] <= pitch, TTS_ERR_INVALID,
-                  "find_endpoint: sentence " + std::to_string(b) + " has N[b] out of range [0, pitch]");
-        // candidates x = k hop, k >= 1, x < N - window
-        if ((int64_t)N[b] - window_length > hop_length)
-            Kmax = std::max(Kmax, (N[b] - window_length - 1) / hop_length);
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    double* wmax;
-    int* iw;  // N [B], end [B]
-    {
-        tts_status st = tts::silence_workspace(g, (size_t)B * Kmax, (size_t)2 * B, &wmax, &iw);
-        if (st) return st;
-    }
-    TTS_HIP(hipMemcpyAsync(iw, N, B * sizeof(int), hipMemcpyHostToDevice, s));
-    TTS_HIP(tts::silence_endpoint(wav, pitch, iw, B, window_length, hop_length, threshold, wmax, Kmax, iw + B, s));
-    TTS_HIP(hipMemcpyAsync(end_out, iw + B, B * sizeof(int), hipMemcpyDeviceToHost, s));
-    TTS_HIP(hipStreamSynchronize(s));
-    return TTS_OK;
-}
-
-tts_status tts_gl_take_segments(tts_gl* g, const double* src, int64_t src_pitch, const int32_t* start,
-                                const int32_t* len, int B, double* dst, int64_t dst_pitch, void* stream) {
-    TTS_CHECK(g && src && start && len && dst, TTS_ERR_INVALID, "take_segments: null argument");
-    TTS_CHECK(B >= 1 && B <= 65535, TTS_ERR_INVALID, "take_segments: B out of range [1, 65535]");
-    TTS_CHECK(dst_pitch >= 1 && dst_pitch <= INT32_MAX, TTS_ERR_INVALID, "take_segments: dst_pitch out of range");
-    for (int b = 0; b < B; ++b) {
-        TTS_CHECK(start[b] >= 0 && len[b] >= 0, TTS_ERR_INVALID,
-                  "take_segments: sentence " + std::to_string(b) + " has a negative start or len");
-        TTS_CHECK((int64_t)start[b] + len[b] <= src_pitch, TTS_ERR_INVALID,
-                  "take_segments: sentence " + std::to_string(b) + " has start + len > src_pitch");
-        TTS_CHECK(len[b] <= dst_pitch, TTS_ERR_INVALID,
-                  "take_segments: sentence " + std::to_string(b) + " has len > dst_pitch");
-    }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (2 * B > g->seg_n) {
-        TTS_HIP(hipStreamSynchronize(s));  // (the previous gather on this stream may still read it)
-        if (g->seg) TTS_HIP(hipFree(g->seg));
-        g->seg = nullptr;
-        g->seg_n = 0;
-        TTS_HIP(hipMalloc(&g->seg, 2 * B * sizeof(int)));
-        g->seg_n = 2 * B;
-    }
-    g->seg_h.assign(start, start + B);
-    g->seg_h.insert(g->seg_h.end(), len, len + B);
-    TTS_HIP(hipMemcpyAsync(g->seg, g->seg_h.data(), 2 * B * sizeof(int), hipMemcpyHostToDevice, s));
-    TTS_HIP(tts::silence_take_segments(src, src_pitch, g->seg, B, dst, dst_pitch, s));
-    return TTS_OK;
-}
-
-}  // extern "C"
-
-namespace tts {
 // tts_gl_run, optionally with the frame counts also on the device (F_dev, the same values as F:
 // tts_synth_run passes the decoder's step counts at r = 1): the persistent loop's launches then
 // read them there and the upload is skipped (the graph-replayed fallbacks still upload into the
@@ -2463,388 +2066,69 @@ tts_status gl_run_dev(tts_gl* g, int mode, const float* spec, const int32_t* F, 
     TTS_CHECK(mode == TTS_GL_FROM_MEL || mode == TTS_GL_FROM_LINEAR, TTS_ERR_INVALID, "bad mode");
     TTS_CHECK(mode == TTS_GL_FROM_LINEAR || g->pinv, TTS_ERR_INVALID, "mel mode needs inv_mel_basis at create");
     for (int b = 0; b < B; ++b) TTS_CHECK(F[b] >= 2 && F[b] <= Fmax, TTS_ERR_INVALID, "F[b] out of range [2, Fmax]");
-    hipStream_t cs = stream;
-    hipStream_t s = g->pipeline ? cs : g->stream;
-    const Geo geo = g->g;
-    const int64_t Nmax = (int64_t)geo.hop * (Fmax - 1);
-    {
-        tts_status pst = gl_collect(g);  // the previous pipeline run, if any (its status, timing)
-        if (pst) return pst;
-    }
-    // workspace (grow only; graphs bake the buffer addresses and are dropped when they move)
-    const size_t needS = (size_t)B * Fmax * NB, needF = (size_t)2 * B * Fmax * geo.winp, needY = (size_t)B * Nmax;
-    bool moved = false;
-    auto grow = [&](void** p, size_t& have, size_t need, size_t elem) -> tts_status {
-        if (need <= have) return TTS_OK;
-        if (*p) TTS_HIP(hipFree(*p));
-        *p = nullptr;
-        TTS_HIP(hipMalloc(p, need * elem));
-        have = need;
-        moved = true;
-        return TTS_OK;
-    };
-    // the workspace may move below: nothing of this handle may still be in flight (a pipeline
-    // run's stream has been synchronised by its caller before the next run)
-    if (!g->pipeline) TTS_HIP(hipStreamSynchronize(s));
-    tts_status st;
-    if ((st = grow(reinterpret_cast<void**>(&g->S), g->S_n, needS, sizeof(spec_t)))) return st;
-    if ((st = grow(reinterpret_cast<void**>(&g->frames), g->fr_n, needF, sizeof(frame_t)))) return st;
-    if ((st = grow(reinterpret_cast<void**>(&g->y), g->y_n, needY, 4))) return st;
-    if (B > g->Fcap_B) {
-        if (g->F) TTS_HIP(hipFree(g->F));
-        g->F = nullptr;
-        TTS_HIP(hipMalloc(&g->F, B * sizeof(int)));
-        g->Fcap_B = B;
-        moved = true;
-    }
-    if (moved) {
-        for (auto& kv : g->graphs) (void)hipGraphExecDestroy(kv.second);
-        g->graphs.clear();
-    }
-    if (s != cs) {
-        TTS_HIP(hipEventRecord(g->ev_in, cs));
-        TTS_HIP(hipStreamWaitEvent(s, g->ev_in, 0));
-    }
+    RunCtx c{};
+    c.mode = mode; c.spec = spec; c.F = F; c.F_dev = F_dev; c.F_bound = F_bound;
+    c.B = B; c.Fmax = Fmax; c.iters = iters;
+    c.phase_u = phase_u; c.seed = seed; c.wav = wav;
+    c.cs = stream;
+    c.s = g->pipeline ? stream : g->stream;
+    c.Nmax = (int64_t)g->g.hop * (Fmax - 1);
+    c.fstride = (size_t)B * Fmax * g->g.winp;
+    c.timed = !g->pipeline;
+    TTS_TRY(gl_collect(g));  // the previous pipeline run, if any (its status, timing)
+    TTS_TRY(reserve_workspace(g, c));
     // path choice (host values only): small batches fuse the overlap-add into the iteration launch;
     // at most 512 frames in all run the whole loop as one persistent launch
-    const char* fz = getenv("TTS_GL_FUSED");
-    const bool fused = gl_fused_path(g, B, Fmax);
-    int frames_total = 0;
-    for (int b = 0; b < B; ++b) frames_total += F[b];
-    const bool persistent = gl_persistent_path(g, B, Fmax, frames_total, iters);
+    c.fused = gl_fused_path(g, B, Fmax);
+    for (int b = 0; b < B; ++b) c.frames_total += F[b];
+    c.persistent = gl_persistent_path(g, B, Fmax, c.frames_total, iters);
     // the launches read the frame counts from F_dev when the persistent loop takes them all; the
-    // graph-replayed loops read the handle's own array, filled from F_dev when there is one (a
-    // speculative run's host F is only an upper bound: tts_synth_run)
-    const int* Fd = persistent && F_dev ? F_dev : g->F;  // (reassigned if the persistent launch falls back)
-    if (Fd == g->F) {
-        if (F_bound) TTS_HIP(hipMemcpyAsync(g->F, F_dev, B * sizeof(int), hipMemcpyDeviceToDevice, s));
-        else TTS_HIP(hipMemcpyAsync(g->F, F, B * sizeof(int), hipMemcpyHostToDevice, s));
+    // graph-replayed loops read the handle's own array, which their graphs bake in
+    c.Fd = c.persistent && F_dev ? F_dev : g->F.p;
+    if (c.Fd == g->F.p) TTS_TRY(stage_counts(g, c));
+    TTS_TRY(draw_phases(g, c));
+    TTS_TRY(launch_magnitude(g, c));
+    TTS_TRY(launch_init(g, c));
+    if (c.persistent) TTS_TRY(run_persistent(g, c));
+    if (!c.persistent_ran && c.Fd != g->F.p) {  // not placed: the fallbacks' graphs read the handle's array
+        TTS_TRY(stage_counts(g, c));
+        c.Fd = c.ia.F = c.fa.F = g->F.p;
     }
-    if (!phase_u && g->mt_armed) {
-        // the reference's np.random.rand draws, continued on the device from numpy's state
-        // (tts_gl_set_phase_state): one [1025][F_b] draw per sentence in batch order
-        const size_t needP = (size_t)B * NB * Fmax;
-        if (needP > g->mt_phase_n) {
-            if (g->mt_stream) TTS_HIP(hipStreamSynchronize(g->mt_stream));  // an earlier run may still read it
-            if (g->mt_phase) TTS_HIP(hipFree(g->mt_phase));
-            g->mt_phase = nullptr;
-            TTS_HIP(hipMalloc(&g->mt_phase, needP * sizeof(double)));
-            g->mt_phase_n = needP;
-        }
-        if ((st = mt_draw(g, Fd, B, Fmax, g->mt_phase, s))) return st;
-        phase_u = g->mt_phase;
-    }
-    MagArgs ma{};
-    ma.mode = mode;
-    ma.spec = spec;
-    ma.n_in = mode == TTS_GL_FROM_MEL ? g->cfg.num_mels : NB;
-    ma.Fmax = Fmax;
-    ma.F = Fd;
-    ma.pinv = g->pinv;
-    ma.S = g->S;
-    ma.min_db = g->cfg.min_level_db;
-    ma.ref_db = g->cfg.ref_level_db;
-    ma.power = g->cfg.power;
-    ma.max_norm = g->cfg.max_norm;
-    ma.signal_norm = g->cfg.signal_norm;
-    ma.symmetric = g->cfg.symmetric_norm;
-    ma.clip = g->cfg.clip_norm;
-    if (mode == TTS_GL_FROM_LINEAR)
-        hipLaunchKernelGGL(gl_linear_magnitude_kernel,
-                           dim3((unsigned)(((int64_t)Fmax * NB + 256 * LIN_PER - 1) / (256 * LIN_PER)), B), dim3(256), 0, s,
-                           ma);
-    else
-        hipLaunchKernelGGL(gl_magnitude_kernel, dim3((NB + MAG_KT - 1) / MAG_KT, (Fmax + MAG_FT - 1) / MAG_FT, B),
-                           dim3(256), 0, s, ma);
-    TTS_HIP(hipGetLastError());
-    const size_t fstride = (size_t)B * Fmax * geo.winp;
-    // the persistent loop reads and writes two slots of tagged granules (gl_persistent_kernel);
-    // the other loops two slots of float32 frames (TTS_GL_FUSED=1 forces the fused form at any
-    // batch: measurement knob)
-    if (persistent && 2 * fstride > g->pgr_n) {
-        if (g->pgr) TTS_HIP(hipFree(g->pgr));
-        g->pgr = nullptr;
-        TTS_HIP(hipMalloc(&g->pgr, 2 * fstride * sizeof(gran_t)));
-        g->pgr_n = 2 * fstride;
-        // fresh memory may hold a freed handle's granules, and every handle's salts start at 1: a
-        // stale granule there can carry a tag this handle is about to wait for.  Filled with a word
-        // that is no live tag and not 0 (0 marks an absent contributor: gl_persistent_kernel)
-        TTS_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(g->pgr), GL_GRAN_FILL, g->pgr_n * 2, s));
-    }
-    // frame slot i of the two ping-pong slots of the fused / batched loops
-    auto slot = [&](int i) -> void* { return static_cast<frame_t*>(g->frames) + (i & 1) * fstride; };
-    if (persistent) {  // the initial iSTFT tags its granules with the launch's salt
-        g->salt = (g->salt + 1) & 0x3FFFF;
-        if (g->salt == 0) {
-            // wrapped: a granule of the launch 2^18 back could carry a current tag
-            g->salt = 1;
-            TTS_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(g->pgr), GL_GRAN_FILL, g->pgr_n * 2, s));
-        }
-    }
-    IterArgs ia{};
-    ia.S = g->S;
-    ia.F = Fd;
-    ia.Fmax = Fmax;
-    ia.B = B;
-    ia.g = geo;
-    ia.c = GLConst{g->win, g->win2, g->tw};
-    ia.phase_u = phase_u;
-    ia.seed = seed;
-    ia.y = g->y;
-    ia.Nmax = Nmax;
-    ia.next = persistent ? static_cast<void*>(g->pgr) : slot(0);
-    ia.wt = g->wt;
-    ia.winc = g->winc;
-    ia.wrot = g->wrot;
-    ia.gtag = g->salt << 14;
-    if (persistent) {
-        if ((size_t)B * Fmax > g->flags_n) {
-            if (g->flags) TTS_HIP(hipFree(g->flags));
-            g->flags = nullptr;
-            TTS_HIP(hipMalloc(&g->flags, sizeof(unsigned) * (size_t)B * Fmax));
-            g->flags_n = (size_t)B * Fmax;
-        }
-        // table entries are salted per launch, and a new handle can get a freed one's words: the
-        // initial iSTFT launch zeroes them and the status word
-        ia.zero_flags = g->flags;
-        ia.zero_status = g->pstatus;
-    }
-    const dim3 grid(Fmax, B), block(GL_THREADS);
-    static const bool wave_init = [] {  // measurement: TTS_GL_WAVE_INIT=0 keeps the block-kernel init
-        const char* v = getenv("TTS_GL_WAVE_INIT");
-        return !(v && v[0] == '0');
-    }();
-    if (persistent) hipLaunchKernelGGL((gl_iter_kernel<true, false, gran_t>), grid, block, 0, s, ia);
-    else if (!fused && g->wave && wave_init)  // the batched loop's own layout for its first launch
-        hipLaunchKernelGGL(gl_iter_wave_kernel<true>, grid, dim3(64), 0, s, ia);
-    else hipLaunchKernelGGL((gl_iter_kernel<true, false, frame_t>), grid, block, 0, s, ia);
-    ia.zero_flags = nullptr;
-    ia.zero_status = nullptr;
-    TTS_HIP(hipGetLastError());
-    // loop timers and the completion event outside pipeline mode only (each event marker holds the
-    // GPU ~5.8 us between the kernels around it); a pipeline run's status travels by sequence word
-    const bool timed = !g->pipeline;
-    if (timed) TTS_HIP(hipEventRecord(g->ev_t0, s));
-    FinArgs fa{};
-    fa.F = Fd;
-    fa.Fmax = Fmax;
-    fa.B = B;
-    fa.g = geo;
-    fa.c = ia.c;
-    fa.y = g->y;
-    fa.Nmax = Nmax;
-    fa.wssp = g->wssp;
-    const dim3 ogrid((Nmax + 255) / 256, B), oblock(256);
-    bool persistent_ran = false;
-    if (persistent) {
-        PersArgs pa{};
-        pa.it = ia;
-        pa.frames = g->pgr;
-        pa.fstride = (int64_t)fstride;
-        pa.iters = iters;
-        pa.xtab = g->flags;
-        pa.salt = g->salt;
-        pa.tmo = g->tmo;
-        pa.status = g->pstatus;
-        pa.drop_f = -1;
-        if (const char* inj = getenv("TTS_GL_INJECT_DROP"); inj && inj[0]) pa.drop_f = atoi(inj);
-        static const bool gl_nowait = [] {
-            const char* v = getenv("TTS_GL_NOWAIT");
-            return v && v[0] == '1';
-        }();
-        pa.nowait = gl_nowait;
-        static const int gl_first_sleep = [] {
-            const char* v = getenv("TTS_GL_FIRST_SLEEP");
-            return v ? atoi(v) : 4;  // round 6: -19 us per configs[1] sentence (tools/cases_sleep.txt)
-        }();
-        pa.first_sleep = gl_first_sleep;
-        long long* prof = nullptr;
-        const char* phases = getenv("TTS_GL_PHASES");
-        if (phases && phases[0]) {  // diagnostic: phase ticks of frame TTS_GL_PHASES (stderr)
-            TTS_HIP(hipMalloc(&prof, 6 * sizeof(long long)));
-            TTS_HIP(hipMemsetAsync(prof, 0, 6 * sizeof(long long), s));
-            pa.prof = prof;
-            pa.prof_f = std::min(atoi(phases), frames_total - 1);
-        }
-        // every workgroup waits on its neighbours inside the launch: co-residency guaranteed, or
-        // nothing runs and the fused loop below takes the iterations (bitwise the same waveform)
-        void* kargs[] = {&pa};
-        // dynamic LDS: the gather buffer, GL_SLOTS frame slots + the zero word
-        const size_t og_bytes = ((size_t)GL_SLOTS * geo.winp + 2) * sizeof(float);
-        // up to 256 workgroups: one per compute unit; up to 512: two per compute unit (gl_persistent2_kernel)
-        const bool two = (long long)grid.x * grid.y > 256;
-        const void* pfn = two ? reinterpret_cast<const void*>(&gl_persistent2_kernel)
-                              : reinterpret_cast<const void*>(&gl_persistent_kernel);
-        static const hipError_t attr = [] {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gl_persistent_kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gl_persistent2_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            return e;
-        }();
-        TTS_HIP(attr);
-        TTS_CHECK(og_bytes <= 96 * 1024, TTS_ERR_INVALID, "persistent Griffin-Lim: window too long for the gather buffer");
-        TTS_HIP(launch_persistent(pfn, grid, block, kargs, og_bytes, s, &persistent_ran));
-        if (!persistent_ran) {
-            // the initial iSTFT wrote slot 0 of the granule buffer: hand it to the fused loop
-            hipLaunchKernelGGL(gl_gran_to_frames_kernel, dim3((unsigned)((fstride + 255) / 256)), dim3(256), 0, s,
-                               g->pgr, static_cast<frame_t*>(g->frames), (int64_t)fstride);
-            TTS_HIP(hipGetLastError());
-            if (prof) {
-                TTS_HIP(hipStreamSynchronize(s));
-                TTS_HIP(hipFree(prof));
-                prof = nullptr;
-            }
-        }
-        if (prof) {
-            long long h[6];
-            TTS_HIP(hipMemcpyAsync(h, prof, sizeof(h), hipMemcpyDeviceToHost, s));
-            TTS_HIP(hipStreamSynchronize(s));
-            TTS_HIP(hipFree(prof));
-            int rate_khz = 100000, dev = 0;
-            (void)hipGetDevice(&dev);
-            (void)hipDeviceGetAttribute(&rate_khz, hipDeviceAttributeWallClockRate, dev);
-            static const char* names[6] = {"gather", "ola_sums", "fwd_fft", "spectrum", "inv_fft", "store"};
-            fprintf(stderr, "TTS_GL_PHASES frame %d, us per iteration:", pa.prof_f);
-            for (int k = 0; k < 6; ++k) fprintf(stderr, " %s %.3f", names[k], h[k] * 1e3 / rate_khz / iters);
-            fprintf(stderr, "\n");
-        }
-    }
-    if (!persistent_ran && Fd != g->F) {
-        // the persistent loop could not be placed: its fallbacks replay graphs that bake the
-        // handle's own frame-count array in
-        if (F_bound) TTS_HIP(hipMemcpyAsync(g->F, F_dev, B * sizeof(int), hipMemcpyDeviceToDevice, s));
-        else TTS_HIP(hipMemcpyAsync(g->F, F, B * sizeof(int), hipMemcpyHostToDevice, s));
-        Fd = g->F;
-        ia.F = fa.F = Fd;
-    }
-    if (!persistent_ran && iters > 0) {
-        // one iteration = overlap-add of the previous frames into the float32 signal (every
-        // sample once) + one workgroup per frame for STFT -> phase -> iSTFT of that signal
-        GraphKey key{B, Fmax, iters};
-        auto it = g->graphs.find(key);
-        if (it == g->graphs.end()) {
-            hipGraph_t graph = nullptr;
-            TTS_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            for (int i = 0; i < iters; ++i) {
-                IterArgs a = ia;
-                a.phase_u = nullptr;
-                a.next = slot(i + 1);
-                if (fused) {
-                    a.prev = slot(i);
-                    hipLaunchKernelGGL((gl_iter_kernel<false, true, frame_t>), grid, block, 0, s, a);
-                } else {
-                    FinArgs o = fa;
-                    o.frames = slot(i);
-                    launch_ola_frames(o, s);
-                    if (g->wave)
-                        hipLaunchKernelGGL(gl_iter_wave_kernel<false>, grid, dim3(64), 0, s, a);
-                    else
-                        hipLaunchKernelGGL((gl_iter_kernel<false, false, frame_t>), grid, block, 0, s, a);
-                }
-            }
-            hipError_t ce = hipGetLastError();
-            hipError_t ee = hipStreamEndCapture(s, &graph);
-            TTS_HIP(ce);
-            TTS_HIP(ee);
-            hipGraphExec_t exec = nullptr;
-            TTS_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-            TTS_HIP(hipGraphDestroy(graph));
-            it = g->graphs.emplace(key, exec).first;
-        }
-        TTS_HIP(hipGraphLaunch(it->second, s));
-    }
-    if (timed) TTS_HIP(hipEventRecord(g->ev_t1, s));
-    fa.frames = persistent_ran ? static_cast<void*>(g->pgr + (size_t)(iters & 1) * fstride) : slot(iters);
-    fa.status = persistent_ran ? g->pstatus : nullptr;
-    fa.host_status = persistent_ran ? g->host_status : nullptr;  // (no read-back copy launch)
-    if (persistent_ran && !timed) {
-        fa.host_seq = g->host_status + 1;
-        fa.seq = ++g->seq;
-        g->seq_stream = s;
-    }
-    if (persistent_ran) hipLaunchKernelGGL(gl_ola_kernel<gran_t>, ogrid, oblock, 0, s, fa);
-    else launch_ola_frames(fa, s);
-    fa.status = nullptr;
-    fa.host_status = nullptr;
-    fa.host_seq = nullptr;
-    TTS_HIP(hipGetLastError());
-    {
-        // de-emphasis chunks: each starts `look` samples early, |c|^look <= 1e-22; one chunk per
-        // sentence (look 0) when that does not fit one scan tile
-        const double c = g->cfg.preemphasis, ac = std::fabs(c);
-        int64_t chunk = SCAN_CHUNK, look = 0;
-        if (ac > 0.0) {
-            const double need = ac < 1.0 ? std::ceil(std::log(1e-22) / std::log(ac)) : 1e30;
-            if (need <= (double)(SCAN_THREADS * SCAN_PER - SCAN_CHUNK - 8)) look = (int64_t)need;
-            else chunk = Nmax;
-        }
-        const dim3 sgrid((unsigned)((Nmax + chunk - 1) / chunk), B);
-        hipLaunchKernelGGL(preemph_scan_kernel, sgrid, dim3(SCAN_THREADS), 0, s, g->y, Nmax, Fd, geo.hop, c,
-                           c != 0.0 ? 1 : 0, chunk, look, wav);
-    }
-    TTS_HIP(hipGetLastError());
-    g->last_persistent = persistent_ran;
-    g->last_path = persistent_ran ? TTS_GL_PATH_PERSISTENT : fused ? TTS_GL_PATH_FUSED : TTS_GL_PATH_UNFUSED;
-    g->last_launches = persistent_ran ? 1 : (fused ? 1 : 2) * iters;
-    if (timed) {
-        TTS_HIP(hipEventRecord(g->ev_done, s));
-        if (s != cs) TTS_HIP(hipStreamWaitEvent(cs, g->ev_done, 0));
-    } else {
-        g->last_ms = 0.f;  // (pipeline mode: not timed)
-    }
-    g->last_timed = timed;
-    g->pending = true;
-    if (!g->pipeline) {
-        tts_status cst = gl_collect(g);
-        if (cst) return cst;
-    }
-    g->last_fused = fused;
-    g->have_last = true;
-    g->last_iter = ia;
-    g->last_fin = fa;
-    g->last_fstride = fstride;
-    return TTS_OK;
+    if (!c.persistent_ran && iters > 0) TTS_TRY(run_graph_loop(g, c));
+    TTS_TRY(finish(g, c));
+    return record_last(g, c);
 }
 
 }  // namespace tts
 
 extern "C" {
 
+tts_status tts_gl_run(tts_gl* g, int mode, const float* spec, const int32_t* F, int B, int Fmax,
+                      const double* phase_u, uint64_t seed, int iters, double* wav, void* stream) {
+    return tts::gl_run_dev(g, mode, spec, F, nullptr, B, Fmax, phase_u, seed, iters, wav, static_cast<hipStream_t>(stream));
+}
+
 tts_status tts_gl_profile(tts_gl* g, int reps, float* kernel_ms, int n_kernels) {
     TTS_CHECK(g && kernel_ms && n_kernels >= TTS_GL_KERNELS && reps >= 1, TTS_ERR_INVALID, "bad profile arguments");
     TTS_CHECK(g->have_last, TTS_ERR_INVALID, "tts_gl_profile needs a previous tts_gl_run");
-    {
-        tts_status pst = gl_collect(g);
-        if (pst) return pst;
-    }
+    TTS_TRY(gl_collect(g));
     hipStream_t s = g->stream;
     hipEvent_t ev[3];
     for (auto& e : ev) TTS_HIP(hipEventCreate(&e));
-    const IterArgs& ia = g->last_iter;
-    const dim3 grid(ia.Fmax, ia.B), block(GL_THREADS);
     double it_ms = 0.0, ola_ms = 0.0;
     for (int r = 0; r < reps; ++r) {
         // one GL iteration as tts_gl_run launches it: overlap-add -> per-frame STFT/iSTFT
         FinArgs f = g->last_fin;
-        const size_t es = sizeof(frame_t);
-        f.frames = static_cast<char*>(g->frames) + (r & 1) * g->last_fstride * es;
-        IterArgs a = ia;
+        f.frames = g->frames.p + (r & 1) * g->last_fstride;
+        IterArgs a = g->last_iter;
         a.phase_u = nullptr;
-        a.next = static_cast<char*>(g->frames) + ((r + 1) & 1) * g->last_fstride * es;
+        a.next = g->frames.p + ((r + 1) & 1) * g->last_fstride;
         a.prev = f.frames;
         TTS_HIP(hipEventRecord(ev[0], s));
-        if (!g->last_fused)
-            launch_ola_frames(f, s);
+        if (!g->last_fused) launch_ola_frames(f, s);
         TTS_HIP(hipGetLastError());
         TTS_HIP(hipEventRecord(ev[1], s));
-        if (g->last_fused)
-            hipLaunchKernelGGL((gl_iter_kernel<false, true, frame_t>), grid, block, 0, s, a);
-        else if (g->wave)
-            hipLaunchKernelGGL(gl_iter_wave_kernel<false>, grid, dim3(64), 0, s, a);
-        else
-            hipLaunchKernelGGL((gl_iter_kernel<false, false, frame_t>), grid, block, 0, s, a);
+        launch_iteration(g->last_fused, g->wave, a, s);
         TTS_HIP(hipGetLastError());
         TTS_HIP(hipEventRecord(ev[2], s));
         TTS_HIP(hipEventSynchronize(ev[2]));
@@ -2857,179 +2141,6 @@ tts_status tts_gl_profile(tts_gl* g, int reps, float* kernel_ms, int n_kernels) 
     for (auto& e : ev) (void)hipEventDestroy(e);
     kernel_ms[0] = (float)(it_ms / reps);
     kernel_ms[1] = (float)(ola_ms / reps);
-    return TTS_OK;
-}
-
-
-tts_status tts_gl_set_mel_basis(tts_gl* g, const double* mel_basis) {
-    TTS_CHECK(g && mel_basis, TTS_ERR_INVALID, "null argument");
-    const int M = g->cfg.num_mels;
-    const size_t n = (size_t)M * NB;
-    // each row's nonzero bins [first, last): linear_to_mel_kernel sums only inside them
-    std::vector<int> band(2 * (size_t)M, 0);
-    int lo = NB, hi = 0;
-    for (int m = 0; m < M; ++m) {
-        const double* row = mel_basis + (size_t)m * NB;
-        int k0 = 0, k1 = NB;
-        while (k0 < NB && row[k0] == 0.0) ++k0;
-        while (k1 > k0 && row[k1 - 1] == 0.0) --k1;
-        if (k0 == NB) continue;  // an empty filter
-        band[2 * m] = k0;
-        band[2 * m + 1] = k1;
-        lo = std::min(lo, k0);
-        hi = std::max(hi, k1);
-    }
-    if (!g->band) TTS_HIP(hipMalloc(&g->band, band.size() * sizeof(int)));
-    if (!g->basis) TTS_HIP(hipMalloc(&g->basis, n * sizeof(double)));
-    TTS_HIP(hipStreamSynchronize(g->stream));  // a conversion still reading the previous basis
-    TTS_HIP(hipMemcpy(g->band, band.data(), band.size() * sizeof(int), hipMemcpyHostToDevice));
-    TTS_HIP(hipMemcpy(g->basis, mel_basis, n * sizeof(double), hipMemcpyHostToDevice));
-    g->band_lo = std::min(lo, hi);
-    g->band_hi = hi;
-    return TTS_OK;
-}
-
-}  // extern "C"
-
-namespace tts {
-namespace {
-
-// the per-sentence counts of an analysis / conversion call, on the device (g->stream)
-tts_status upload_counts(tts_gl* g, const int32_t* v, int B, hipStream_t s) {
-    if (B > g->NS_cap) {
-        TTS_HIP(hipStreamSynchronize(s));
-        if (g->NS) TTS_HIP(hipFree(g->NS));
-        g->NS = nullptr;
-        g->NS_cap = 0;
-        TTS_HIP(hipMalloc(&g->NS, B * sizeof(int)));
-        g->NS_cap = B;
-    }
-    TTS_HIP(hipMemcpyAsync(g->NS, v, B * sizeof(int), hipMemcpyHostToDevice, s));
-    return TTS_OK;
-}
-
-NormArgs norm_args(const tts_audio_config& c) {
-    NormArgs n{};
-    n.min_db = c.min_level_db;
-    n.min_level = std::exp((double)c.min_level_db / 20.0 * std::log(10.0));  // utils/audio.py:122
-    n.ref_db = c.ref_level_db;
-    n.max_norm = c.max_norm;
-    n.signal_norm = c.signal_norm;
-    n.symmetric = c.symmetric_norm;
-    n.clip = c.clip_norm;
-    return n;
-}
-
-// tts_gl_analyze / tts_gl_melspectrogram: one launch, one FFT per frame, either or both outputs
-tts_status gl_analyze(tts_gl* g, const double* wav, const int32_t* N, int B, int64_t Nmax, float* lin, float* mel,
-                      int Fmax, void* stream) {
-    TTS_CHECK(g && wav && N && B >= 1 && Fmax >= 1, TTS_ERR_INVALID, "bad analysis arguments");
-    TTS_CHECK(lin || mel, TTS_ERR_INVALID, "analysis needs at least one output");
-    TTS_CHECK(!mel || g->basis, TTS_ERR_INVALID, "mel analysis needs tts_gl_set_mel_basis first");
-    TTS_CHECK(B <= 65535, TTS_ERR_INVALID, "B > 65535");
-    for (int b = 0; b < B; ++b) {
-        TTS_CHECK(N[b] >= 2 && N[b] <= Nmax, TTS_ERR_INVALID, "N[b] out of range [2, Nmax]");
-        TTS_CHECK(1 + N[b] / g->g.hop <= Fmax, TTS_ERR_INVALID, "Fmax < 1 + N[b] / hop");
-    }
-    hipStream_t cs = static_cast<hipStream_t>(stream);
-    hipStream_t s = g->stream;
-    TTS_HIP(hipEventRecord(g->ev_in, cs));
-    TTS_HIP(hipStreamWaitEvent(s, g->ev_in, 0));
-    {
-        tts_status st = upload_counts(g, N, B, s);
-        if (st) return st;
-    }
-    MelArgs a{};
-    a.wav = wav;
-    a.Nmax = Nmax;
-    a.N = g->NS;
-    a.Fmax = Fmax;
-    a.g = g->g;
-    a.c = GLConst{g->win, g->win2, g->tw};
-    a.basis = g->basis;
-    a.n_mels = g->cfg.num_mels;
-    a.coef = g->cfg.preemphasis;
-    a.n = norm_args(g->cfg);
-    a.lin = lin;
-    a.mel = mel;
-    const dim3 grid(Fmax, B), block(GL_THREADS);
-    if (lin && mel)
-        hipLaunchKernelGGL((analysis_kernel<true, true>), grid, block, 0, s, a);
-    else if (lin)
-        hipLaunchKernelGGL((analysis_kernel<true, false>), grid, block, 0, s, a);
-    else
-        hipLaunchKernelGGL((analysis_kernel<false, true>), grid, block, 0, s, a);
-    TTS_HIP(hipGetLastError());
-    TTS_HIP(hipEventRecord(g->ev_out, s));
-    TTS_HIP(hipStreamWaitEvent(cs, g->ev_out, 0));
-    return TTS_OK;
-}
-
-}  // namespace
-}  // namespace tts
-
-extern "C" {
-
-tts_status tts_gl_melspectrogram(tts_gl* g, const double* wav, const int32_t* N, int B, int64_t Nmax, float* mel,
-                                 int Fmax, void* stream) {
-    TTS_CHECK(mel, TTS_ERR_INVALID, "bad melspectrogram arguments");
-    return gl_analyze(g, wav, N, B, Nmax, nullptr, mel, Fmax, stream);
-}
-
-tts_status tts_gl_analyze(tts_gl* g, const double* wav, const int32_t* N, int B, int64_t Nmax, float* linear,
-                          float* mel, int Fmax, void* stream) {
-    return gl_analyze(g, wav, N, B, Nmax, linear, mel, Fmax, stream);
-}
-
-tts_status tts_gl_linear_to_mel(tts_gl* g, const float* linear, const int32_t* F, int B, int Fmax, float* mel,
-                                void* stream) {
-    TTS_CHECK(g && linear && F && mel && B >= 1 && Fmax >= 1, TTS_ERR_INVALID, "bad linear_to_mel arguments");
-    TTS_CHECK(g->basis && g->band, TTS_ERR_INVALID, "tts_gl_linear_to_mel needs tts_gl_set_mel_basis first");
-    TTS_CHECK(B <= 65535, TTS_ERR_INVALID, "B > 65535");
-    for (int b = 0; b < B; ++b) TTS_CHECK(F[b] >= 1 && F[b] <= Fmax, TTS_ERR_INVALID, "F[b] out of range [1, Fmax]");
-    hipStream_t cs = static_cast<hipStream_t>(stream);
-    hipStream_t s = g->stream;
-    TTS_HIP(hipEventRecord(g->ev_in, cs));
-    TTS_HIP(hipStreamWaitEvent(s, g->ev_in, 0));
-    {
-        tts_status st = upload_counts(g, F, B, s);
-        if (st) return st;
-    }
-    L2MArgs a{};
-    a.lin = linear;
-    a.F = g->NS;
-    a.Fmax = Fmax;
-    a.basis = g->basis;
-    a.band = g->band;
-    a.k_lo = g->band_lo;
-    a.k_hi = g->band_hi;
-    a.n_mels = g->cfg.num_mels;
-    a.min_db = g->cfg.min_level_db;
-    a.ref_db = g->cfg.ref_level_db;
-    a.max_norm = g->cfg.max_norm;
-    a.n = norm_args(g->cfg);
-    a.mel = mel;
-    hipLaunchKernelGGL(linear_to_mel_kernel, dim3((Fmax + L2M_TF - 1) / L2M_TF, B), dim3(L2M_THREADS), 0, s, a);
-    TTS_HIP(hipGetLastError());
-    TTS_HIP(hipEventRecord(g->ev_out, s));
-    TTS_HIP(hipStreamWaitEvent(cs, g->ev_out, 0));
-    return TTS_OK;
-}
-
-tts_status tts_gl_last_path(tts_gl* g, int* path) {
-    TTS_CHECK(g && path, TTS_ERR_INVALID, "null argument");
-    *path = g->last_path;
-    return TTS_OK;
-}
-
-tts_status tts_gl_last_timing(tts_gl* g, float* loop_ms, int* launches) {
-    TTS_CHECK(g && loop_ms && launches, TTS_ERR_INVALID, "null argument");
-    {
-        tts_status pst = gl_collect(g);
-        if (pst) return pst;
-    }
-    *loop_ms = g->last_ms;
-    *launches = g->last_launches;
     return TTS_OK;
 }
 

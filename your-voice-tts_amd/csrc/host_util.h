@@ -56,6 +56,26 @@ struct DeviceAllocs {
     }
 };
 
+// A grow-only device block of T.  reserve(need) keeps a block that holds `need` elements; else it
+// frees it, allocates `need` and sets *moved.  The pointer is null and the capacity 0 between the
+// two, so a failed hipMalloc leaves the owner destroyable.  What has to happen before a block may
+// move (a stream still reading it) is the caller's: test cap first.
+template <typename T>
+struct DeviceBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    tts_status reserve(size_t need, bool* moved = nullptr) {
+        if (need <= cap) return TTS_OK;
+        if (p) TTS_HIP(hipFree(p));
+        p = nullptr;
+        cap = 0;
+        TTS_HIP(hipMalloc(&p, need * sizeof(T)));
+        cap = need;
+        if (moved) *moved = true;
+        return TTS_OK;
+    }
+};
+
 // A device copy of a checkpoint tensor in its reference layout.
 inline tts_status copy_weight(DeviceAllocs& dev, float** dst, const float* src, size_t n, hipStream_t s) {
     TTS_TRY(dev.alloc(dst, n));

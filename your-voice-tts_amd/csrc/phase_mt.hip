@@ -31,7 +31,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "common.h"
+#include "gl_handle.h"
 
 namespace tts {
 namespace {
@@ -197,7 +197,11 @@ void mt_work_free(MtWork* w) {
     *w = MtWork{};
 }
 
-hipError_t mt_draw_phases(unsigned* state, const int* F_dev, int B, int Fmax, double* out, MtWork* w, hipStream_t s) {
+// numpy's legacy np.random.rand(1025, F[b]) draws for b = 0..B-1 in order, continued from the MT19937
+// state `state` ([dev] 624 key words + position, updated in place) into out [dev] fp64 [B][1025][Fmax]
+// (F_dev on the device, read on stream s).  The stream is cut into chunks of MT_CHUNK key blocks, each
+// started by a GF(2) jump-ahead and generated by its own workgroup.
+static hipError_t mt_draw_phases(unsigned* state, const int* F_dev, int B, int Fmax, double* out, MtWork* w, hipStream_t s) {
     if (B < 1 || B > MT_MAX_BATCH || Fmax < 0) return hipErrorInvalidValue;
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&mt_chunk_kernel),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)CHUNK_SMEM);
@@ -244,4 +248,61 @@ hipError_t mt_draw_phases(unsigned* state, const int* F_dev, int B, int Fmax, do
     return hipGetLastError();
 }
 
+// (gl_handle.h) draws on another stream than the last one wait for it: the stream's order is the draws' order
+tts_status mt_draw(tts_gl* g, const int* F_dev, int B, int Fmax, double* out, hipStream_t s) {
+    TTS_CHECK(B <= MT_MAX_BATCH, TTS_ERR_UNSUPPORTED, "numpy-stream phases: at most 1024 sentences per run");
+    if (g->mt_stream && g->mt_stream != s) TTS_HIP(hipStreamWaitEvent(s, g->ev_mt, 0));
+    TTS_HIP(mt_draw_phases(g->mt_state, F_dev, B, Fmax, out, &g->mt_work, s));
+    TTS_HIP(hipEventRecord(g->ev_mt, s));
+    g->mt_stream = s;
+    return TTS_OK;
+}
+
 }  // namespace tts
+
+using namespace tts;
+
+extern "C" {
+
+tts_status tts_gl_set_phase_state(tts_gl* g, const uint32_t* key, int pos) {
+    TTS_CHECK(g, TTS_ERR_INVALID, "null handle");
+    if (!key) {
+        g->mt_armed = false;
+        return TTS_OK;
+    }
+    TTS_CHECK(pos >= 0 && pos <= 624, TTS_ERR_INVALID, "MT19937 position must be in [0, 624]");
+    if (!g->mt_state) TTS_HIP(hipMalloc(&g->mt_state, 625 * sizeof(unsigned)));
+    if (g->mt_stream) TTS_HIP(hipEventSynchronize(g->ev_mt));  // a draw may still read the old state
+    unsigned h[625];
+    std::copy(key, key + 624, h);
+    h[624] = (unsigned)pos;
+    TTS_HIP(hipMemcpy(g->mt_state, h, sizeof(h), hipMemcpyHostToDevice));
+    g->mt_armed = true;
+    return TTS_OK;
+}
+
+tts_status tts_gl_get_phase_state(tts_gl* g, uint32_t* key, int* pos) {
+    TTS_CHECK(g && key && pos, TTS_ERR_INVALID, "null argument");
+    TTS_CHECK(g->mt_state, TTS_ERR_INVALID, "no phase state set (tts_gl_set_phase_state)");
+    if (g->mt_stream) TTS_HIP(hipEventSynchronize(g->ev_mt));
+    unsigned h[625];
+    TTS_HIP(hipMemcpy(h, g->mt_state, sizeof(h), hipMemcpyDeviceToHost));
+    std::copy(h, h + 624, key);
+    *pos = (int)h[624];
+    return TTS_OK;
+}
+
+tts_status tts_gl_draw_phases(tts_gl* g, const int32_t* F, int B, int Fmax, double* phase_u, void* stream) {
+    TTS_CHECK(g && F && phase_u && B >= 1 && Fmax >= 1, TTS_ERR_INVALID, "bad draw_phases arguments");
+    TTS_CHECK(g->mt_armed, TTS_ERR_INVALID, "no phase state set (tts_gl_set_phase_state)");
+    for (int b = 0; b < B; ++b) TTS_CHECK(F[b] >= 0 && F[b] <= Fmax, TTS_ERR_INVALID, "F[b] out of range [0, Fmax]");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // (mt_F is rewritten below: a draw on another stream may still read it)
+    if (g->mt_stream && g->mt_stream != s) TTS_HIP(hipStreamWaitEvent(s, g->ev_mt, 0));
+    if ((size_t)B > g->mt_F.cap && g->mt_stream) TTS_HIP(hipEventSynchronize(g->ev_mt));
+    TTS_TRY(g->mt_F.reserve(B));
+    TTS_HIP(hipMemcpyAsync(g->mt_F.p, F, B * sizeof(int), hipMemcpyHostToDevice, s));
+    return mt_draw(g, g->mt_F.p, B, Fmax, phase_u, s);
+}
+
+}  // extern "C"

@@ -13,7 +13,7 @@
 // N[b].  Integers out; nothing here depends on the order workgroups run in.
 #include <cmath>
 
-#include "common.h"
+#include "gl_handle.h"
 
 namespace tts {
 namespace {
@@ -178,39 +178,114 @@ __global__ __launch_bounds__(SIL_THREADS) void take_segments_kernel(const SegArg
     a.dst[(int64_t)b * a.dst_pitch + i] = i < len ? a.src[(int64_t)b * a.src_pitch + start + i] : 0.0;
 }
 
+// the silence workspace: `values` doubles, then `ints` ints (grow only; idle whenever a call begins,
+// since both calls that use it wait for their stream before they return)
+tts_status silence_workspace(tts_gl* g, size_t values, size_t ints, double** v, int** i) {
+    TTS_TRY(g->sil.reserve(values * sizeof(double) + ints * sizeof(int)));
+    *v = reinterpret_cast<double*>(g->sil.p);
+    *i = reinterpret_cast<int*>(*v + values);
+    return TTS_OK;
+}
 }  // namespace
 
-// N_dev [dev] int [B]; ms [dev] fp64 [B][Fmax], Fmax >= 1 + (N[b] - 2 margin) / hop; out [dev] int [2][B]
-hipError_t silence_trim(const double* wav, int64_t pitch, const int* N_dev, int B, int margin, int frame_length,
-                        int hop, double top_db, double* ms, int Fmax, int* out, hipStream_t s) {
-    TrimArgs a{wav, pitch, N_dev, margin, frame_length, hop, top_db, ms, Fmax, out, B};
+}  // namespace tts
+
+using namespace tts;
+
+extern "C" {
+
+tts_status tts_gl_trim_silence(tts_gl* g, const double* wav, int64_t pitch, const int32_t* N, int B, int margin,
+                               int frame_length, int hop_length, double top_db, int32_t* start_out,
+                               int32_t* end_out, void* stream) {
+    TTS_CHECK(g && wav && N && start_out && end_out, TTS_ERR_INVALID, "trim_silence: null argument");
+    TTS_CHECK(B >= 1 && B <= 65535, TTS_ERR_INVALID, "trim_silence: B out of range [1, 65535]");
+    TTS_CHECK(margin >= 0 && frame_length >= 2 && frame_length % 2 == 0 && hop_length >= 1, TTS_ERR_INVALID,
+              "trim_silence: margin must be >= 0, frame_length positive and even, hop_length positive");
+    int Fmax = 1;
+    for (int b = 0; b < B; ++b) {
+        TTS_CHECK(N[b] <= pitch, TTS_ERR_INVALID, "trim_silence: sentence " + std::to_string(b) + " has N[b] > pitch");
+        TTS_CHECK(N[b] >= 2 * (int64_t)margin, TTS_ERR_INVALID,
+                  "trim_silence: sentence " + std::to_string(b) + " is shorter than its two margins");
+        const int n = N[b] - 2 * margin;
+        TTS_CHECK(n >= frame_length / 2 + 1, TTS_ERR_INVALID,
+                  "trim_silence: sentence " + std::to_string(b) + " has " + std::to_string(n) +
+                      " samples between the margins, fewer than frame_length / 2 + 1 = " +
+                      std::to_string(frame_length / 2 + 1) + " (the reflect padding needs one reflection)");
+        Fmax = std::max(Fmax, 1 + n / hop_length);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double* ms;
+    int* iw;  // N [B], start [B], end [B]
+    TTS_TRY(silence_workspace(g, (size_t)B * Fmax, (size_t)3 * B, &ms, &iw));
+    TTS_HIP(hipMemcpyAsync(iw, N, B * sizeof(int), hipMemcpyHostToDevice, s));
+    TrimArgs a{wav, pitch, iw, margin, frame_length, hop_length, top_db, ms, Fmax, iw + B, B};
     hipLaunchKernelGGL(trim_frames_kernel, dim3((Fmax + SIL_WAVES - 1) / SIL_WAVES, B), dim3(SIL_THREADS), 0, s, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    TTS_HIP(hipGetLastError());
     hipLaunchKernelGGL(trim_select_kernel, dim3(B), dim3(SIL_THREADS), 0, s, a);
-    return hipGetLastError();
+    TTS_HIP(hipGetLastError());
+    TTS_HIP(hipMemcpyAsync(start_out, iw + B, B * sizeof(int), hipMemcpyDeviceToHost, s));
+    TTS_HIP(hipMemcpyAsync(end_out, iw + 2 * B, B * sizeof(int), hipMemcpyDeviceToHost, s));
+    TTS_HIP(hipStreamSynchronize(s));
+    return TTS_OK;
 }
 
-// wmax [dev] fp64 [B][Kmax], Kmax >= every sentence's candidate count (may be 0: no window launch); out [dev] int [B]
-hipError_t silence_endpoint(const double* wav, int64_t pitch, const int* N_dev, int B, int window, int hop,
-                            double threshold, double* wmax, int Kmax, int* out, hipStream_t s) {
-    EndArgs a{wav, pitch, N_dev, window, hop, threshold, wmax, Kmax, out};
-    if (Kmax > 0) {
+tts_status tts_gl_find_endpoint(tts_gl* g, const double* wav, int64_t pitch, const int32_t* N, int B,
+                                int window_length, int hop_length, double threshold, int32_t* end_out,
+                                void* stream) {
+    TTS_CHECK(g && wav && N && end_out, TTS_ERR_INVALID, "find_endpoint: null argument");
+    TTS_CHECK(B >= 1 && B <= 65535, TTS_ERR_INVALID, "find_endpoint: B out of range [1, 65535]");
+    TTS_CHECK(window_length >= 1 && hop_length >= 1, TTS_ERR_INVALID,
+              "find_endpoint: window_length and hop_length must be positive");
+    int Kmax = 0;
+    for (int b = 0; b < B; ++b) {
+        TTS_CHECK(N[b] >= 0 && N[b] <= pitch, TTS_ERR_INVALID,
+                  "find_endpoint: sentence " + std::to_string(b) + " has N[b] out of range [0, pitch]");
+        // candidates x = k hop, k >= 1, x < N - window
+        if ((int64_t)N[b] - window_length > hop_length)
+            Kmax = std::max(Kmax, (N[b] - window_length - 1) / hop_length);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    double* wmax;
+    int* iw;  // N [B], end [B]
+    TTS_TRY(silence_workspace(g, (size_t)B * Kmax, (size_t)2 * B, &wmax, &iw));
+    TTS_HIP(hipMemcpyAsync(iw, N, B * sizeof(int), hipMemcpyHostToDevice, s));
+    EndArgs a{wav, pitch, iw, window_length, hop_length, threshold, wmax, Kmax, iw + B};
+    if (Kmax > 0) {  // (0: no sentence has a candidate window)
         hipLaunchKernelGGL(end_window_kernel, dim3(Kmax, B), dim3(SIL_THREADS), 0, s, a);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
+        TTS_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(end_select_kernel, dim3(B), dim3(SIL_THREADS), 0, s, a);
-    return hipGetLastError();
+    TTS_HIP(hipGetLastError());
+    TTS_HIP(hipMemcpyAsync(end_out, iw + B, B * sizeof(int), hipMemcpyDeviceToHost, s));
+    TTS_HIP(hipStreamSynchronize(s));
+    return TTS_OK;
 }
 
-// seg [dev] int [2][B]: start, len (start + len <= src_pitch, len <= dst_pitch, dst_pitch >= 1)
-hipError_t silence_take_segments(const double* src, int64_t src_pitch, const int* seg, int B, double* dst,
-                                 int64_t dst_pitch, hipStream_t s) {
-    SegArgs a{src, src_pitch, seg, B, dst, dst_pitch};
+tts_status tts_gl_take_segments(tts_gl* g, const double* src, int64_t src_pitch, const int32_t* start,
+                                const int32_t* len, int B, double* dst, int64_t dst_pitch, void* stream) {
+    TTS_CHECK(g && src && start && len && dst, TTS_ERR_INVALID, "take_segments: null argument");
+    TTS_CHECK(B >= 1 && B <= 65535, TTS_ERR_INVALID, "take_segments: B out of range [1, 65535]");
+    TTS_CHECK(dst_pitch >= 1 && dst_pitch <= INT32_MAX, TTS_ERR_INVALID, "take_segments: dst_pitch out of range");
+    for (int b = 0; b < B; ++b) {
+        TTS_CHECK(start[b] >= 0 && len[b] >= 0, TTS_ERR_INVALID,
+                  "take_segments: sentence " + std::to_string(b) + " has a negative start or len");
+        TTS_CHECK((int64_t)start[b] + len[b] <= src_pitch, TTS_ERR_INVALID,
+                  "take_segments: sentence " + std::to_string(b) + " has start + len > src_pitch");
+        TTS_CHECK(len[b] <= dst_pitch, TTS_ERR_INVALID,
+                  "take_segments: sentence " + std::to_string(b) + " has len > dst_pitch");
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // (the previous gather on this stream may still read it)
+    if ((size_t)2 * B > g->seg.cap) TTS_HIP(hipStreamSynchronize(s));
+    TTS_TRY(g->seg.reserve(2 * B));
+    g->seg_h.assign(start, start + B);
+    g->seg_h.insert(g->seg_h.end(), len, len + B);
+    TTS_HIP(hipMemcpyAsync(g->seg.p, g->seg_h.data(), 2 * B * sizeof(int), hipMemcpyHostToDevice, s));
+    SegArgs a{src, src_pitch, g->seg.p, B, dst, dst_pitch};
     hipLaunchKernelGGL(take_segments_kernel, dim3((unsigned)((dst_pitch + SIL_THREADS - 1) / SIL_THREADS), B),
                        dim3(SIL_THREADS), 0, s, a);
-    return hipGetLastError();
+    TTS_HIP(hipGetLastError());
+    return TTS_OK;
 }
 
-}  // namespace tts
+}  // extern "C"

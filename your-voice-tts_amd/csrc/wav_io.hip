@@ -7,7 +7,7 @@
 // finds) and one pass that writes the int16 samples with the gaps in place.  The arithmetic is
 // numpy's: the scale is one float64 division, each sample one float64 product truncated toward
 // zero (the C conversion astype(int16) performs), so the bytes equal the reference's.
-#include "common.h"
+#include "gl_handle.h"
 
 namespace tts {
 namespace {
@@ -72,22 +72,36 @@ __global__ __launch_bounds__(PCM_THREADS) void pcm_write_kernel(const PcmArgs a)
 }
 
 }  // namespace
+}  // namespace tts
 
-// start: [dev] B + 1 output offsets (start[b + 1] - start[b] = n_b + gap); peak_bits: [dev] one
-// word, overwritten (peak >= 0: that peak is used, else max |y| over the request)
-hipError_t pcm16_join(const double* wav, int64_t pitch, const int64_t* start_dev, int64_t total, int B, int gap,
-                      double peak, unsigned long long* peak_bits, int16_t* out, hipStream_t s) {
-    PcmArgs a{wav, pitch, start_dev, B, gap, peak_bits, peak, out};
-    hipError_t e;
+using namespace tts;
+
+extern "C" {
+
+tts_status tts_gl_save_pcm16(tts_gl* g, const double* wav, int64_t pitch, const int64_t* n, int B, int gap,
+                             double peak, int16_t* out, void* stream) {
+    TTS_CHECK(g && wav && n && out && B >= 1 && gap >= 0, TTS_ERR_INVALID, "bad save_pcm16 arguments");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    for (int b = 0; b < B; ++b) TTS_CHECK(n[b] >= 0 && n[b] <= pitch, TTS_ERR_INVALID, "n[b] out of range [0, pitch]");
+    if (!g->pcm_peak) TTS_HIP(hipMalloc(&g->pcm_peak, sizeof(unsigned long long)));
+    // (the previous join on this stream may still read the offsets)
+    if ((size_t)B + 1 > g->pcm_start.cap) TTS_HIP(hipStreamSynchronize(s));
+    TTS_TRY(g->pcm_start.reserve(B + 1));
+    g->pcm_start_h.assign(B + 1, 0);
+    for (int b = 0; b < B; ++b) g->pcm_start_h[b + 1] = g->pcm_start_h[b] + n[b] + gap;
+    TTS_HIP(hipMemcpyAsync(g->pcm_start.p, g->pcm_start_h.data(), (B + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    // the peak word is overwritten (peak >= 0: that peak is used, else max |y| over the request)
+    PcmArgs a{wav, pitch, g->pcm_start.p, B, gap, g->pcm_peak, peak, out};
     if (peak < 0.0) {
-        if ((e = hipMemsetAsync(peak_bits, 0, sizeof(*peak_bits), s)) != hipSuccess) return e;
+        TTS_HIP(hipMemsetAsync(g->pcm_peak, 0, sizeof(*g->pcm_peak), s));
         hipLaunchKernelGGL(pcm_peak_kernel, dim3(64, B), dim3(PCM_THREADS), 0, s, a);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+        TTS_HIP(hipGetLastError());
     }
-    const int64_t per_block = (int64_t)PCM_THREADS * PCM_PER;
+    const int64_t total = g->pcm_start_h[B], per_block = (int64_t)PCM_THREADS * PCM_PER;
     if (total > 0)
         hipLaunchKernelGGL(pcm_write_kernel, dim3((unsigned)((total + per_block - 1) / per_block)), dim3(PCM_THREADS), 0, s, a);
-    return hipGetLastError();
+    TTS_HIP(hipGetLastError());
+    return TTS_OK;
 }
 
-}  // namespace tts
+}  // extern "C"
