@@ -458,6 +458,50 @@ tts_status tts_tacotron_resident_phases(tts_tacotron* t, float* us, int n);
 #define TTS_TACOTRON_STEP_KERNELS 9
 tts_status tts_tacotron_profile(tts_tacotron* t, int reps, float* kernel_ms, int n_kernels);
 
+/* ---------------------------------------------------------------- evaluation losses
+ * The criteria of train.py:462-465 as evaluate() applies them (train.py:327-339), on tensors that stay in
+ * HBM: one read of every valid element of both operands, no masked copies, three numbers out.  The handle
+ * carries the partials workspace: one fp64 partial per 8192-element chunk of work, grown on demand. */
+typedef struct tts_loss tts_loss;
+tts_status tts_loss_create(tts_loss** out);
+void tts_loss_destroy(tts_loss* l);
+
+#define TTS_LOSS_L1 0   /* L1LossMasked (layers/losses.py:7-33); nn.L1Loss when lengths is NULL   */
+#define TTS_LOSS_MSE 1  /* MSELossMasked (layers/losses.py:36-62); nn.MSELoss when lengths is NULL */
+
+/* Replaces sequence_mask + input * mask + target * mask + l1_loss / mse_loss (reduction="sum") + mask.sum()
+ * + the division (layers/losses.py:27-33, 56-62; five passes over [B][T][D] and three tensors of that size
+ * in the reference), and nn.L1Loss() / nn.MSELoss() (train.py:464) when lengths is NULL (every row counts).
+ *   input, target [dev]  fp32 [B][T][D], rows contiguous (T * D floats per sentence), sentence b at
+ *                        b * pitch elements: a decoder output view need not be contiguous over B
+ *   lengths       [host] int32 [B] or NULL; sentence b contributes rows t < min(lengths[b], T)
+ *   per_sentence  [dev]  fp64 [B] out: each sentence's sum of |x - y| or (x - y)^2 (0 without valid rows)
+ *   loss_dev      [dev]  fp32 out: *loss_out rounded once
+ *   sum_out, count_out, loss_out [host] out: the sum over all sentences, the number of terms
+ *                        D * sum_b min(lengths[b], T) (mask.sum() as an integer), and sum / count; a count
+ *                        of 0 gives NaN, as the reference's 0 / 0 does
+ * The difference, its absolute value or square and every accumulation are fp64, from the fp32 operands.
+ * The summation order is a function of the element index alone (wave reduction, one fp64 partial per
+ * chunk, a second launch that folds the partials; no floating-point atomics, no hand-off inside a
+ * launch), so the results are bitwise the same run to run and for any pitches and base addresses.
+ * Rows at and beyond a sentence's length are NOT READ: they are padding, and at D = 1025 they are half the
+ * traffic of a ragged batch.  One consequence differs from the reference: a NaN in the padding does not
+ * reach the result here, while the reference's NaN * 0 does.
+ * INVALID before any launch, outputs untouched: a null pointer (lengths excepted), a kind that is neither,
+ * B, T or D <= 0, a pitch below T * D, a negative length.  Waits for the stream before it returns. */
+tts_status tts_loss_masked(tts_loss* l, int kind, const float* input, int64_t input_pitch, const float* target,
+                           int64_t target_pitch, const int32_t* lengths, int B, int T, int D, double* per_sentence,
+                           float* loss_dev, double* sum_out, int64_t* count_out, double* loss_out, void* stream);
+
+/* Replaces nn.BCEWithLogitsLoss() with its defaults on the stop logits (train.py:327, 465): the mean over
+ * the n values of max(x, 0) - x y + log1p(exp(-|x|)), in fp64 from the fp32 operands, by the same two
+ * launches (exp's argument is never positive: nothing overflows at any |x|).
+ *   logits, targets [dev] fp32 [n]; sum_dev [dev] fp64 out: the sum; loss_dev [dev] fp32 out: *loss_out
+ *   rounded once; sum_out, loss_out [host] out: the sum and sum / n.
+ * INVALID before any launch: a null pointer, n <= 0.  Waits for the stream before it returns. */
+tts_status tts_loss_bce_logits(tts_loss* l, const float* logits, const float* targets, int64_t n, double* sum_dev,
+                               float* loss_dev, double* sum_out, double* loss_out, void* stream);
+
 const char* tts_last_error(void);
 const char* tts_version(void);
 

@@ -9,6 +9,9 @@ interface for the path:
 * ``synthesis.synthesis / tts``     <- ``utils/synthesis.py``, ``synthesize.py``
 * ``synthesis.Synthesizer``         <- ``server/synthesizer.py``
 * ``generic_utils.load_config / setup_model`` <- ``utils/generic_utils.py``
+* ``datasets.collate_fn``, ``data.prepare_*`` <- ``datasets/TTSDataset.py``, ``utils/data.py``
+* ``losses.L1LossMasked / MSELossMasked``     <- ``layers/losses.py``
+* ``evaluate.evaluate_batch / evaluate``      <- ``train.py`` (``evaluate``)
 
 The directory name is not a Python identifier; import with
 ``importlib.import_module("your-voice-tts_amd")``.  Importing is cheap; the native library is
@@ -18,4 +21,5 @@ import sys as _sys
 
 _sys.modules.setdefault("yvtts_amd", _sys.modules[__name__])
 
-__all__ = ["weights", "generic_utils", "tacotron2", "audio", "synthesis", "sharding"]
+__all__ = ["weights", "generic_utils", "tacotron2", "audio", "synthesis", "sharding", "data", "datasets", "losses",
+           "evaluate"]

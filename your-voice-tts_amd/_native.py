@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("TTS_HIP_LIB", os.path.join(_HERE, "libtts_hip.so"))
 
 TTS_GL_FROM_MEL = 0
 TTS_GL_FROM_LINEAR = 1
+TTS_LOSS_L1 = 0
+TTS_LOSS_MSE = 1
 GL_PATHS = {0: "unfused", 1: "fused", 2: "persistent"}  # TTS_GL_PATH_* (include/tts_hip.h)
 DECODER_STEP_KERNELS = ("prenet2", "att_lstm", "query", "attention", "dec_lstm", "mel_fused")
 GL_KERNELS = ("gl_iter", "gl_ola")
@@ -37,6 +39,7 @@ EXPORTS = (
     "tts_tacotron_decode_teacher",
     "tts_tacotron_postnet", "tts_tacotron_last_timing", "tts_tacotron_last_path", "tts_tacotron_resident_phases",
     "tts_tacotron_profile",
+    "tts_loss_create", "tts_loss_destroy", "tts_loss_masked", "tts_loss_bce_logits",
     "tts_last_error", "tts_version",
 )
 
@@ -146,6 +149,13 @@ def _declare(lib):
     lib.tts_tacotron_last_path.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
     lib.tts_tacotron_resident_phases.argtypes = [vp, FP, ctypes.c_int]
     lib.tts_tacotron_profile.argtypes = [vp, ctypes.c_int, FP, ctypes.c_int]
+    DP, I64P = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)
+    lib.tts_loss_create.argtypes = [ctypes.POINTER(vp)]
+    lib.tts_loss_destroy.argtypes = [vp]
+    lib.tts_loss_destroy.restype = None
+    lib.tts_loss_masked.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64, I32P, ctypes.c_int,
+                                    ctypes.c_int, ctypes.c_int, vp, vp, DP, I64P, DP, vp]
+    lib.tts_loss_bce_logits.argtypes = [vp, vp, vp, ctypes.c_int64, vp, vp, DP, DP, vp]
     lib.tts_last_error.restype = ctypes.c_char_p
     lib.tts_version.restype = ctypes.c_char_p
     for name in EXPORTS:
@@ -153,7 +163,7 @@ def _declare(lib):
         if name.endswith(("_create", "_run", "_timing", "_profile", "_encode", "_decode", "_postnet", "_state",
                           "_continue", "_basis", "_melspectrogram", "_path", "_sync", "_phases", "_teacher",
                           "_phase_state", "_pcm16", "_limits", "_analyze", "_to_mel", "_silence", "_endpoint",
-                          "_segments")):
+                          "_segments", "_masked", "_logits")):
             fn.restype = ctypes.c_int
 
 

@@ -311,17 +311,19 @@ class AudioProcessor:
             self._mel_basis_set = True
         return lib, h
 
-    def _analyze(self, wav, N, want_linear, want_mel):
-        """tts_gl_analyze: one STFT per frame, either or both of the outputs (None where not asked)."""
+    def _analyze(self, wav, N, want_linear, want_mel, Fmax=None):
+        """tts_gl_analyze: one STFT per frame, either or both of the outputs (None where not asked), Fmax
+        rows per sentence (None: the longest sentence's frames)."""
         lib, h = self._set_mel_basis() if want_mel else self._handle()
         wav = wav.to(torch.float64).contiguous()
         B, Nmax = wav.shape
         F = [1 + int(n) // self.hop_length for n in N]
-        lin = torch.empty(B, max(F), self.n_fft // 2 + 1, device=wav.device) if want_linear else None
-        mel = torch.empty(B, max(F), self.num_mels, device=wav.device) if want_mel else None
+        Fmax = max(F) if Fmax is None else int(Fmax)
+        lin = torch.empty(B, Fmax, self.n_fft // 2 + 1, device=wav.device) if want_linear else None
+        mel = torch.empty(B, Fmax, self.num_mels, device=wav.device) if want_mel else None
         _native.check(lib.tts_gl_analyze(h, ctypes.c_void_p(wav.data_ptr()), _native.i32_array(N), B, Nmax,
                                          ctypes.c_void_p(lin.data_ptr()) if want_linear else None,
-                                         ctypes.c_void_p(mel.data_ptr()) if want_mel else None, max(F),
+                                         ctypes.c_void_p(mel.data_ptr()) if want_mel else None, Fmax,
                                          _native.stream_handle()), "tts_gl_analyze")
         return mel, lin, F
 
@@ -345,10 +347,12 @@ class AudioProcessor:
         _, lin, F = self._analyze(wav, N, True, False)
         return lin, F
 
-    def features_batch(self, wav, N):
+    def features_batch(self, wav, N, Fmax=None):
         """melspectrogram_batch and spectrogram_batch from one STFT per frame, as collate_fn needs them
-        (datasets/TTSDataset.py:191-192).  Returns (mel, linear, frames per sentence)."""
-        return self._analyze(wav, N, True, True)
+        (datasets/TTSDataset.py:191-192).  Returns (mel, linear, frames per sentence).  Fmax: rows per
+        sentence of both outputs (default: the longest sentence's frames); rows at and beyond a sentence's
+        frames are zero, which is collate_fn's zero frame and padding."""
+        return self._analyze(wav, N, True, True, Fmax)
 
     def melspectrogram(self, y):  # utils/audio.py:146-152 -> ndarray [num_mels, frames]
         self._handle()  # raises without a GPU / library: no CPU fallback

@@ -165,6 +165,12 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// fp64 butterfly: one fixed order, and a + b == b + a, so every lane ends with the same bits
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
+    return v;
+}
 // DPP wave reductions (VALU data-parallel-primitive lanes moves: no LDS round trip per level as
 // __shfl_xor's ds_bpermute has).  Inclusive row scans by row_shr 1/2/4/8, then row_bcast:15 and
 // row_bcast:31 carry rows into lane 63; the total is read from lane 63 (wave-uniform result).

@@ -21,11 +21,6 @@ namespace {
 constexpr int SIL_THREADS = 256;
 constexpr int SIL_WAVES = SIL_THREADS / WAVE;
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);  // a + b == b + a: every lane the same bits
-    return v;
-}
 __device__ __forceinline__ double wave_max_f64(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, WAVE));

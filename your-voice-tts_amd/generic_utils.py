@@ -37,6 +37,15 @@ def default_config(name: str = "config_tacotron2.json") -> AttrDict:
     return load_config(os.path.join(CONFIG_DIR, name))
 
 
+def sequence_mask(sequence_length, max_len=None):  # utils/generic_utils.py:209-220
+    """Bool [B, max_len]: position t of row b is True for t < sequence_length[b] (on the lengths' device)."""
+    import torch
+    if max_len is None:
+        max_len = int(sequence_length.max())
+    seq_range = torch.arange(0, max_len, device=sequence_length.device).long()
+    return seq_range.unsqueeze(0) < sequence_length.unsqueeze(1)
+
+
 def setup_model(num_chars, num_speakers_or_c, c=None, **kw):
     if c is None:
         c, num_speakers = num_speakers_or_c, getattr(num_speakers_or_c, "num_speakers", 0) or 0
