@@ -60,7 +60,17 @@ tts_status tts_encoder_run(tts_encoder* e, const int32_t* ids, const int32_t* le
                            float* out, void* stream);
 /* Same with the BiLSTM state carried (Encoder.inference_truncated, layers/tacotron2.py:85-93):
  *   state_in  [dev] fp32 [4][B][256] = (h_fwd, h_bwd, c_fwd, c_bwd) initial state, or NULL (zeros)
- *   state_out [dev] fp32 [4][B][256] final state (h_n, c_n per direction), or NULL. */
+ *   state_out [dev] fp32 [4][B][256] final state (h_n, c_n per direction), or NULL.
+ * Which BiLSTM serves which arguments (reported by tts_encoder_last_path); out and state_out are
+ * the same on every path within fp32 reduction order:
+ *   B == 1, lens[0] == Lmax, state_in given or NULL ..... resident batch-1 launch (1)
+ *   B == 1, lens[0] <  Lmax ............................. per-step launches (0)
+ *   B >= 2, state_in == NULL, state_out given or NULL ... batched resident launch (2), which
+ *                                                         stores h_n / c_n of every sentence itself
+ *   B >= 2, state_in given .............................. per-step launches (0)
+ * A handle created under TTS_RESIDENT=0, or on a device where a resident grid cannot be placed,
+ * serves everything with the per-step launches; a resident launch whose hand-off wait times out is
+ * rerun per-step from the caller's initial state within the same call. */
 tts_status tts_encoder_run_state(tts_encoder* e, const int32_t* ids, const int32_t* lens, int B, int Lmax,
                                  const float* state_in, float* state_out, float* out, void* stream);
 
@@ -71,8 +81,8 @@ tts_status tts_encoder_run_state(tts_encoder* e, const int32_t* ids, const int32
 tts_status tts_encoder_add_speakers(tts_encoder* e, float* enc, const int32_t* lens, const int32_t* speaker_ids, int B,
                                     int Lmax, void* stream);
 
-/* 1 if the last run's BiLSTM took the resident (one co-resident launch) path, 0 for the per-step
- * launches (batches, or a device where the resident grid cannot be co-resident). */
+/* The last run's BiLSTM path: 1 the resident batch-1 launch, 2 the batched resident launch
+ * (2 <= B <= 64), 0 the per-step launches (see tts_encoder_run_state). */
 tts_status tts_encoder_last_path(tts_encoder* e, int* resident);
 
 /* Decoder flags: the arguments of layers/tacotron2.py:98-100 (Decoder.__init__) that change

@@ -5,31 +5,14 @@ TTS_CU_CAP pretends the device has fewer CUs: the grids then cannot be co-reside
 persistent is launched, and each stage must take its multi-launch fallback with unchanged results.
 A persistent Griffin-Lim whose hand-off wait times out (fault injection) must raise and must not
 hand out a plausible waveform."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 from conftest import golden, golden_flags, load_pkg
+from encoder_util import _env
 
 pytestmark = pytest.mark.gpu
-
-
-class _env:
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kv}
-        os.environ.update({k: str(v) for k, v in self.kv.items()})
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _t2():

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN, golden, golden_flags, load_pkg, rel_rms, weights_mod
+from encoder_util import encoder_path
 from oracle.griffin_lim_oracle import AudioOracle
 from oracle.tacotron2_oracle import Tacotron2Oracle
 
@@ -80,6 +81,7 @@ def test_encoder_vs_reference(case):
     m = _model(golden_flags(z))
     L = len(z["ids"])
     enc = m.encode(torch.from_numpy(z["ids"])[None].cuda(), [L])
+    assert encoder_path(m) == 1, "the resident batch-1 BiLSTM did not serve this call"
     assert rel_rms(enc[0].cpu().numpy(), z["enc"]) < MEL_RTOL
 
 
@@ -94,6 +96,7 @@ def test_encoder_ragged_batch():
     for b, z in enumerate(zs):
         ids[b, :lens[b]] = torch.from_numpy(z["ids"])
     enc = m.encode(ids.cuda(), lens).cpu().numpy()
+    assert encoder_path(m) == 2, "the batched resident BiLSTM did not serve this call"
     for b, z in enumerate(zs):
         assert rel_rms(enc[b, :lens[b]], z["enc"]) < MEL_RTOL
         assert np.all(enc[b, lens[b]:] == 0)

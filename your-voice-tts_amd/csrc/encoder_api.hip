@@ -69,10 +69,23 @@ struct tts_encoder {
 
 namespace {
 
+// Output rows past L_b are zero; the BiLSTM writes every row below it.  A kernel and not a
+// hipMemsetAsync: this runs inside graphs that are replayed for the life of the handle, and a
+// replayed memset node was seen to fill the buffer with a stale 16-byte host pattern instead of
+// zeros once other calls (the per-sentence state copies) had come between capture and replay.
+__global__ void zero_rows_past_len_kernel(float* out, int Lmax, const int* T) {
+    const int t = blockIdx.x, b = blockIdx.y;
+    if (t < T[b]) return;
+    reinterpret_cast<float4*>(out + ((size_t)b * Lmax + t) * EDIM)[threadIdx.x] = float4{0.f, 0.f, 0.f, 0.f};
+}
+
 tts_status enqueue_encoder(tts_encoder* e, int B, int Lmax, int frames, hipStream_t s, bool resident = false) {
-    // outputs past L_b are zero (the batch-1 resident form runs one sentence of length Lmax: it
-    // writes every row); the initial LSTM state is set outside the graph (tts_encoder_run_state)
-    if (!(resident && B == 1)) TTS_HIP(hipMemsetAsync(e->out, 0, sizeof(float) * (size_t)B * Lmax * EDIM, s));
+    // (the batch-1 resident form runs one sentence of length Lmax: it writes every row); the
+    // initial LSTM state is set outside the graph (tts_encoder_run_state)
+    if (!(resident && B == 1)) {
+        hipLaunchKernelGGL(zero_rows_past_len_kernel, dim3(Lmax, B), dim3(EDIM / 4), 0, s, e->out, Lmax, e->T);
+        TTS_HIP(hipGetLastError());
+    }
     float* bufs[2] = {e->act0, e->act1};
     for (int l = 0; l < 3; ++l) {
         ConvArgs a{};
@@ -448,6 +461,9 @@ tts_status tts_encoder_run_state(tts_encoder* e, const int32_t* ids, const int32
         ba.B = B;
         ba.Tmax = Lmax;
         ba.out = e->out;
+        ba.hdir = (int64_t)hs;  // h_n / c_n where the done: block reads them
+        ba.h_fin = e->h;
+        ba.c_fin = e->c;
         ba.gran = e->bgran;
         ba.status = reinterpret_cast<int*>(e->bgran + encoder_resident_batch_granules() - 2);
         ba.tmo = e->rtmo;

@@ -34,6 +34,9 @@ struct EncResBatchArgs {
     const int* lens;     // [B]
     int B, Tmax;
     float* out;          // [B][Tmax][512]
+    int64_t hdir;        // per-direction stride of h_fin / c_fin (floats, >= B * 256)
+    float* h_fin;        // [2 parity][2][hdir] h_n of sentence b at [(L_b - 1) & 1][dir][b][256]
+    float* c_fin;        // [2][hdir] c_n at [dir][b][256]
     unsigned long long* gran;  // encoder_resident_batch_granules() u64
     int* status;         // salt << 8 | code on failure (res_status_code)
     long long tmo;

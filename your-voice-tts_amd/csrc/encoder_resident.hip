@@ -379,6 +379,12 @@ __global__ __launch_bounds__(EB_THREADS, 1) void encoder_resident_batch_kernel(c
         __syncthreads();
         if (info[3]) return;
     }
+    // final state of the lane's (unit, sentence): h_n to the slot the per-step launches leave it
+    // in (step L_b - 1 writes parity (L_b - 1) & 1), c_n to c; off the step's chain
+    if (wave < 2 && n < nb) {
+        a.h_fin[(int64_t)((Ln - 1) & 1) * 2 * a.hdir + dir * a.hdir + (int64_t)bsen * H + unit] = hprev;
+        a.c_fin[dir * a.hdir + (int64_t)bsen * H + unit] = cs;
+    }
 }
 
 __global__ void enc_res_pack_kernel(const float* whh_f, const float* whh_b, float4* out) {
