@@ -24,8 +24,12 @@ weights = importlib.import_module("your-voice-tts_amd.weights")
 
 # events 8-11: the synthesis form (partials published, partials gathered, A2, none) | the general form
 # (query row published, none, none, context published)
-EV_SYN = ("P1", "B1", "hatt_pub", "B3", "B4", "hdec_pub", "B6", "pre1_pub", "part_pub", "part_gathered", "att_A2", "unused")
-EV_GEN = EV_SYN[:8] + ("q_pub", "unused", "unused", "ctx_pub")
+# events 12, 13 (both forms): the loop-top work done on wave 0 / wave 3, ahead of the pre1 poll
+EV_TOP = ("looptop_w0", "looptop_w3", "unused", "unused")
+EV_SYN = ("P1", "B1", "hatt_pub", "B3", "B4", "hdec_pub", "B6", "pre1_pub", "part_pub", "part_gathered", "att_A2",
+          "unused") + EV_TOP
+EV_GEN = EV_SYN[:8] + ("q_pub", "unused", "unused", "ctx_pub") + EV_TOP
+STOP_CUS = 8  # workgroups 0-7 are rank 0 of their XCD (the stop CUs) under round-robin placement
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--L", type=int, default=100)
@@ -46,10 +50,21 @@ tr = m.profile_resident_trace().astype(np.float64) / 100.0  # wall clock 100 MHz
 steps = range(8, 60)
 rel = {k: [] for k in EV}
 last = {"hatt_pub": collections.Counter(), "hdec_pub": collections.Counter(), "pre1_pub": collections.Counter()}
-period = []
+period, edge_p1 = [], []
+# the loop top of step t: from this CU's pre1 publish of step t-1 (wave 0) to the stamps ahead of
+# the pre1 poll; P1 after the step's first P1; the stop CUs against the rest
+top = {k: [] for k in ("looptop_w0_rest", "looptop_w0_stop", "looptop_w3_rest", "looptop_w3_stop", "P1_rest", "P1_stop")}
+mmm = lambda v: (v.min(), np.median(v), v.max())
 for t in steps:
     t0 = tr[:, t, 0].min()
     period.append(tr[:, t + 1, 0].min() - t0)
+    edge_p1.append(np.median(tr[:, t + 1, 0]) - np.median(tr[:, t, 7]))
+    for w, k in (("w0", 12), ("w3", 13)):
+        d = tr[:, t, k] - tr[:, t - 1, 7]
+        top[f"looptop_{w}_rest"].append(mmm(d[STOP_CUS:]))
+        top[f"looptop_{w}_stop"].append(mmm(d[:STOP_CUS]))
+    top["P1_rest"].append(mmm(tr[STOP_CUS:, t, 0] - t0))
+    top["P1_stop"].append(mmm(tr[:STOP_CUS, t, 0] - t0))
     for k, name in enumerate(EV):
         v = tr[:, t, k]
         v = v[v > 0]
@@ -60,6 +75,8 @@ for t in steps:
         if name in last:
             last[name][int(np.argmax(tr[:, t, k]))] += 1
 rec = {"us_per_step_trace": float(np.median(period)),
+       "pre1_pub_to_P1_us(median CU to median CU)": round(float(np.median(edge_p1)), 2),
+       "loop_top_us(min,median,max)": {k: [round(float(x), 2) for x in np.median(np.array(v), 0)] for k, v in top.items()},
        "events_rel_step_start_us(min,median,max)": {k: [round(float(x), 2) for x in np.median(np.array(v), 0)]
                                                     for k, v in rel.items() if v},
        "last_cu": {k: v.most_common(6) for k, v in last.items()},

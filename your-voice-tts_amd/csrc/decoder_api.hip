@@ -879,12 +879,14 @@ void fill_resident_args(const tts_decoder* d, const RunCtx& c, ResArgs& ra) {
     // first-poll delays (resident.h; round 6: h_att 5 / h_dec 5 took a configs[1] sentence from
     // 2.65 to 2.29 ms, tools/cases_sleep.txt); TTS_RES_SLEEP_* override them (_Q: the synthesis
     // form's energy-partials gather and the general form's query gather; _CTX, _E: general form only)
-    // The synthesis form's defaults are h_att 4 / h_dec 3: its CUs issue attention operand loads
-    // ahead of the h_att poll, and the tail / alpha bookkeeping of every CU now sits between the
-    // h_dec publish and its poll (profiles/r10_ab_parts.txt); the general form keeps 5 / 5.
+    // The synthesis form's defaults are h_att 0 / h_dec 0: both LSTMs' recurrent partials run inside
+    // those two waits (the decoder LSTM's ahead of the h_att poll, the attention LSTM's ahead of the
+    // h_dec poll, beside the attention operand loads and the tail / alpha bookkeeping) and are the
+    // first-poll delay themselves; any s_sleep on top of them lost (profiles/r11_looptop_parts.txt).
+    // The general form keeps 5 / 5.
     static const int sl_hatt_env = env_int("TTS_RES_SLEEP_HATT", -1), sl_hdec_env = env_int("TTS_RES_SLEEP_HDEC", -1);
-    const int sl_hatt = sl_hatt_env >= 0 ? sl_hatt_env : (d->res_gen ? 5 : 4),
-              sl_hdec = sl_hdec_env >= 0 ? sl_hdec_env : (d->res_gen ? 5 : 3);
+    const int sl_hatt = sl_hatt_env >= 0 ? sl_hatt_env : (d->res_gen ? 5 : 0),
+              sl_hdec = sl_hdec_env >= 0 ? sl_hdec_env : (d->res_gen ? 5 : 0);
     static const int sl_p1 = env_int("TTS_RES_SLEEP_P1", 0), sl_pre2 = env_int("TTS_RES_SLEEP_PRE2", 2),
                      sl_ctx = env_int("TTS_RES_SLEEP_CTX", 0), sl_q = env_int("TTS_RES_SLEEP_Q", 0),
                      sl_e = env_int("TTS_RES_SLEEP_E", 0);

@@ -2,17 +2,22 @@
 //
 // Per step t on compute unit c (512 threads = 8 waves; thread (r = tid/32, ks = tid%32) owns
 // gate row r = g*4 + u of units 4c..4c+3 and the k-slice {i*128 + 4ks .. +4}):
-//   1. attention-LSTM partial over [ctx_{t-1} | h_att_{t-1}]            (all waves, VGPR weights)
+//   1. loop top: general form, both LSTMs' recurrent partials over [ctx_{t-1} | h_att_{t-1}] and
+//      h_dec_{t-1} while pre1 is in flight; synthesis form: nothing, its partials ran inside the
+//      device-wide waits of steps 4 and 10 (step 0's attention partial ahead of the loop)
 //   2. wave 0: wait pre1_t (+ continue flag), prenet-2 row c, publish; gather the 256 rows
 //   3. prenet part, row sums, LSTM cell of units 4c..4c+3, publish h_att_t   (tacotron2.py:195-197)
-//   4. gather h_att_t; 5. four query rows of the XCD's copy (common_layers.py:179); synthesis form:
+//   4. synthesis form: decoder-LSTM partial over h_dec_{t-1} (LDS weights) as the first-poll delay;
+//      gather h_att_t; 5. four query rows of the XCD's copy (common_layers.py:179); synthesis form:
 //      rows rank + 32 m -> lane `rank`'s partial of the 16 candidate energies, XCD-local publish
-//   6. decoder-LSTM partial over [h_att_t | h_dec_{t-1}]                  (LDS weights)
+//   6. decoder-LSTM partial over h_att_t                                   (LDS weights)
 //   7. synthesis form, every CU: gather the XCD's 16 x 32 partials, energies, sigmoid, forward
 //      attention + mask, the five weights, the 512 context channels into its own LDS, the tail
 //      (common_layers.py:178-182, 199-223, 239-253); general form: 7' below, 8. gather ctx_t
 //   9. context part, cell, publish h_dec_t                                (tacotron2.py:206-208)
-//  10. gather h_dec_t (the prenet-1 row weights of step 11 in flight from the XCD's L2);
+//  10. synthesis form: step t+1's attention-LSTM partial over [ctx_t | h_att_t] (VGPR weights) as
+//      the first-poll delay, carried to step 3 of t+1; gather h_dec_t (the prenet-1 row weights of
+//      step 11 in flight from the XCD's L2);
 //  11. every wave: one folded prenet-1 row of this XCD's copy -> XCD-local publish; the XCD's
 //      stop CU (rank 0), wave 3: the stop row -> sigmoid + stop rule -> XCD-local continue flag
 //      (tacotron2.py:214-224, 256-277).  Mel row c of step t is written by wave 4 during step
@@ -499,6 +504,35 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         sm_ = wave_sum_dpp(sm_);
         if (lane == 0 && tt < a.hist_cap) a.mel_hist[(int64_t)tt * a.nmel + c] = sm_ + st[48];
     };
+    // The two LSTMs' partials over the previous step's state (chunk order, accumulator parity and
+    // the final add are pinned: the resident fixtures are bitwise).  Macros, not lambdas: the
+    // general form's kernels then compile to the instructions they had with this text at the loop top.
+    // Attention LSTM over [ctx | h_att] as xctx / xh_att hold them (two accumulators: dependency
+    // chains of 24 FMAs instead of 48)
+#define RES_ATT_PARTIAL(out)                                                                                        \
+    {                                                                                                               \
+        float aa[2] = {0.f, 0.f};                                                                                   \
+        _Pragma("unroll") for (int i = 2; i < 6; ++i)                                                               \
+            aa[i & 1] = dot4(wa[i], ld4(xctx + (i - 2) * 128 + ks * 4), aa[i & 1]);                                 \
+        _Pragma("unroll") for (int i = 6; i < 10; ++i)                                                              \
+            aa[i & 1] = dot4(wa[i], ld4(xh_att + (i - 6) * 128 + ks * 4), aa[i & 1]);                               \
+        asm volatile("" ::: "memory"); /* bound the hoisted LDS loads (register pressure) */                        \
+        _Pragma("unroll") for (int i = 10; i < 14; ++i)                                                             \
+            aa[i & 1] = dot4(wa[i], ld4(xh_att + (i - 6) * 128 + ks * 4), aa[i & 1]);                               \
+        out = aa[0] + aa[1];                                                                                        \
+    }
+    // decoder LSTM over h_dec as xh_dec holds it (chains of 16)
+#define RES_DEC_PARTIAL(out)                                                                                        \
+    {                                                                                                               \
+        float ad[2] = {0.f, 0.f};                                                                                   \
+        _Pragma("unroll 2") for (int i = 8; i < 16; ++i)                                                            \
+            ad[i & 1] = dot4(wdl[(i * 16 + r) * 32 + ks], ld4(xh_dec + (i - 8) * 128 + ks * 4), ad[i & 1]);         \
+        out = ad[0] + ad[1];                                                                                        \
+    }
+    // synthesis form: the attention partial is carried from the previous step's h_dec wait; step 0's
+    // is formed here from the initial context and h_att (a continued run: the carried state)
+    float acc_a_next = 0.f;
+    if constexpr (!GEN) RES_ATT_PARTIAL(acc_a_next)
     int t = 0;
     for (;; ++t) {
         u64* G = a.gran + (t & 1) * GR_TOTAL;          // this step's granules
@@ -515,24 +549,19 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         // prenet-1 tag EP6 computed on its own wrapped count
         const unsigned E = (a.salt << 14) | (((unsigned)t & 2047u) << 3);
         const unsigned EP6 = ((a.salt << 14) | (((unsigned)(t - 1) & 2047u) << 3)) + 6u;
-        // 1) attention LSTM over [ctx_{t-1} | h_att_{t-1}]
-        // (two accumulators each: dependency chains of 24 and 16 FMAs instead of 48 and 32, ahead
-        // of the pre1 poll)
-        float aa[2] = {0.f, 0.f};
-#pragma unroll
-        for (int i = 2; i < 6; ++i) aa[i & 1] = dot4(wa[i], ld4(xctx + (i - 2) * 128 + ks * 4), aa[i & 1]);
-#pragma unroll
-        for (int i = 6; i < 10; ++i) aa[i & 1] = dot4(wa[i], ld4(xh_att + (i - 6) * 128 + ks * 4), aa[i & 1]);
-        asm volatile("" ::: "memory");  // bound the hoisted LDS loads (register pressure)
-#pragma unroll
-        for (int i = 10; i < 14; ++i) aa[i & 1] = dot4(wa[i], ld4(xh_att + (i - 6) * 128 + ks * 4), aa[i & 1]);
-        float acc_a = aa[0] + aa[1];
-        // decoder LSTM over h_dec_{t-1}, also while pre1 is in flight
-        float ad[2] = {0.f, 0.f};
-#pragma unroll 2
-        for (int i = 8; i < 16; ++i)
-            ad[i & 1] = dot4(wdl[(i * 16 + r) * 32 + ks], ld4(xh_dec + (i - 8) * 128 + ks * 4), ad[i & 1]);
-        float acc_d = ad[0] + ad[1];
+        // 1) general form: both LSTMs' recurrent partials while pre1 is in flight.  The synthesis
+        //    form formed them inside the previous device-wide waits (steps 4 and 10): its loop top
+        //    holds nothing but the pre1 poll, so a stop CU's stop row and rule (step 11), which
+        //    precede it on wave 3, are absorbed by the pre1 edge's wait
+        float acc_a, acc_d;
+        if constexpr (GEN) {
+            RES_ATT_PARTIAL(acc_a)
+            RES_DEC_PARTIAL(acc_d)
+        } else {
+            acc_a = acc_a_next;
+        }
+        if (tid == 0) { RES_EV(t, 12) }
+        if (tid == 192) { RES_EV(t, 13) }
         // 2) prenet layer 2: wave 0 gathers this XCD's pre1_t (+ the previous step's continue flag);
         //    every wave computes its row of this XCD's copy, publishes it XCD-locally; wave 0 gathers
         // (waves 0, 1: the 256 rows as pairs; wave 2, lane 0: the flag)
@@ -616,6 +645,13 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
             }
         }
         {
+            // synthesis form: the decoder-LSTM partial over h_dec_{t-1} (xh_dec stays intact until
+            // B3, after which a full-evaluation step reuses it as scratch): useful work that doubles
+            // as the first-poll delay
+            if constexpr (!GEN) {
+                RES_DEC_PARTIAL(acc_d)
+                asm volatile("" : "+v"(acc_d));  // (the sum ends here, not behind the poll at its use)
+            }
             if (wave == 4 && t > 0) mel_row(t - 1);
             for (int i = 0; i < a.sleep_hatt; ++i) __builtin_amdgcn_s_sleep(4);
             float h0, h1;
@@ -662,7 +698,8 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
                 if (tid == 0) { RES_EV(t, 8) }
             }
         }
-        // 6) decoder LSTM over h_att_t (its h_dec_{t-1} half ran at the loop top).  In the synthesis
+        // 6) decoder LSTM over h_att_t (its h_dec_{t-1} half ran at the loop top, in the synthesis
+        //    form inside the h_att wait).  In the synthesis
         //    form the energy partials are crossing the XCD meanwhile (useful work that doubles as
         //    the first-poll delay of their gather): there as two rounds of four chunks whose eight
         //    LDS reads are in flight together (left to itself the compiler waits for every chunk's
@@ -1074,8 +1111,17 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
             if (tid < L) anew[tid] = wdef;
             if (att_log && t < a.hist_cap && tid < a.Lalign) a.align_hist[(int64_t)t * a.Lalign + tid] = wdef;
         }
-        // 10) gather h_dec_t
+        // 10) gather h_dec_t; the synthesis form first forms step t+1's attention-LSTM partial over
+        //     [ctx_t | h_att_t] (xctx complete since B4, xh_att since B3): useful work that doubles
+        //     as the first-poll delay.  It is carried across B6, the prenet-1 rows and P1 to step 3
+        //     of t+1 (the last step's is unused).  The empty asm ends the sum here: left alone the
+        //     compiler sinks the 48 FMAs to their use in step t+1 and keeps the twelve loaded
+        //     operands live across the step's end (45 spilled registers)
         {
+            if constexpr (!GEN) {
+                RES_ATT_PARTIAL(acc_a_next)
+                asm volatile("" : "+v"(acc_a_next));
+            }
             for (int i = 0; i < a.sleep_hdec; ++i) __builtin_amdgcn_s_sleep(4);
             float h0, h1;
             const bool ok = sweep_pair(rg, (t & 1) * GR_TOTAL + GR_HDEC + 2 * pk, true, E + 5, h0, h1, tmo);

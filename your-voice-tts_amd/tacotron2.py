@@ -472,15 +472,16 @@ class Tacotron2:
 
     def profile_resident_trace(self):
         """Per-CU event trace of the last resident sentence, re-run with event stamps only
-        (measurement only): int64 numpy [256 CU, 64 steps, 12 events] of wall-clock ticks (P1, B1,
+        (measurement only): int64 numpy [256 CU, 64 steps, 16 events] of wall-clock ticks (P1, B1,
         h_att published, B3, B4, h_dec published, B6, pre1 row published; synthesis form: partials
         published, partials gathered, A2, unused; general form: query row published, unused,
-        unused, context published; 0 = not reached)."""
+        unused, context published; both: loop-top work done on wave 0 and on wave 3, ahead of the
+        pre1 poll; two unused; 0 = not reached)."""
         lib, hdec, _ = self._handles(1, 1)
-        n = 256 * 64 * 12
+        n = 256 * 64 * 16
         buf = (ctypes.c_longlong * n)()
         _native.check(lib.tts_decoder_resident_trace(hdec, buf, n), "tts_decoder_resident_trace")
-        return np.frombuffer(buf, dtype=np.int64).reshape(256, 64, 12).copy()
+        return np.frombuffer(buf, dtype=np.int64).reshape(256, 64, 16).copy()
 
     def profile_step_kernels(self, reps=50):
         """Mean duration (ms) of each decoder-step kernel, HIP events on its own stream, for the
