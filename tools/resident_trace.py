@@ -26,8 +26,9 @@ weights = importlib.import_module("your-voice-tts_amd.weights")
 # (query row published, none, none, context published)
 # events 12, 13 (both forms): the loop-top work done on wave 0 / wave 3, ahead of the pre1 poll
 EV_TOP = ("looptop_w0", "looptop_w3", "unused", "unused")
+# event 14 (synthesis form): the next step's attention operand loads issued (wave 6, end of the step)
 EV_SYN = ("P1", "B1", "hatt_pub", "B3", "B4", "hdec_pub", "B6", "pre1_pub", "part_pub", "part_gathered", "att_A2",
-          "unused") + EV_TOP
+          "unused") + EV_TOP[:2] + ("operands_issued", "unused")
 EV_GEN = EV_SYN[:8] + ("q_pub", "unused", "unused", "ctx_pub") + EV_TOP
 STOP_CUS = 8  # workgroups 0-7 are rank 0 of their XCD (the stop CUs) under round-robin placement
 

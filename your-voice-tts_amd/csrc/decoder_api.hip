@@ -881,7 +881,8 @@ void fill_resident_args(const tts_decoder* d, const RunCtx& c, ResArgs& ra) {
     // form's energy-partials gather and the general form's query gather; _CTX, _E: general form only)
     // The synthesis form's defaults are h_att 0 / h_dec 0: both LSTMs' recurrent partials run inside
     // those two waits (the decoder LSTM's ahead of the h_att poll, the attention LSTM's ahead of the
-    // h_dec poll, beside the attention operand loads and the tail / alpha bookkeeping) and are the
+    // h_dec poll, beside the tail / alpha bookkeeping; the attention operand loads left the h_att
+    // wait for the step's end, re-swept 0 / 1 / 2: profiles/r12_ab_parts.txt) and are the
     // first-poll delay themselves; any s_sleep on top of them lost (profiles/r11_looptop_parts.txt).
     // The general form keeps 5 / 5.
     static const int sl_hatt_env = env_int("TTS_RES_SLEEP_HATT", -1), sl_hdec_env = env_int("TTS_RES_SLEEP_HDEC", -1);

@@ -22,6 +22,10 @@
 //      stop CU (rank 0), wave 3: the stop row -> sigmoid + stop rule -> XCD-local continue flag
 //      (tacotron2.py:214-224, 256-277).  Mel row c of step t is written by wave 4 during step
 //      t+1's h_att gather (after the loop for the last step).
+//  12. synthesis form, waves 3-7 (no poll of theirs before step t+1's h_att gather): step t+1's
+//      attention operands, the entering encoder row and P at the candidate positions, in flight
+//      during the pre1 and prenet-2 edges; those of the polling waves 0-2 reach them through LDS
+//      (written ahead of B2, read after it).
 // Reductions keep fixed orders (bitwise run-to-run deterministic).
 #include "handoff.h"
 #include "resident.h"
@@ -190,8 +194,12 @@ constexpr int SM_ST = 64;                  // biases, cell states, stop-rule sta
 constexpr int SM_RQ = 4 * 64 * 4;          // synthesis form: attention scratch | general form: weights, energies
 constexpr int SM_RM = 2 * 6 * 64 * 4 + 2 * 256;  // mel row c, stop row: [2][6][64] float4 | general form: cumulative weights
 constexpr int SM_PROF = 2 * 16;            // RES_PHASES tick accumulators (long long)
-constexpr int SM_FLOATS = SM_WDL + HATT + HDEC + (ENC + 16) + PRE + ADIM + 16 + 16 + SM_ST + SM_RQ + SM_RM + SM_PROF + PRE;
-static_assert(SM_RQ >= 3 * RES_LMAX + 2 * RES_WAVES + 16 + ADIM, "synthesis form: attention scratch");
+constexpr int RES_POLL_WAVES = 3;           // waves 0-2 poll between B6 and the h_att gather (pre1, prenet-2)
+constexpr int SM_OPR = RES_POLL_WAVES * 64;  // synthesis form: their channels of the entering encoder row
+constexpr int SM_FLOATS = SM_WDL + HATT + HDEC + (ENC + 16) + PRE + ADIM + 16 + 16 + SM_ST + SM_RQ + SM_RM + SM_PROF + PRE + SM_OPR;
+static_assert(SM_FLOATS * 4 <= 160 * 1024, "the CU's LDS");
+static_assert(SM_RQ >= 3 * RES_LMAX + 2 * RES_WAVES + 16 + ADIM + 64, "synthesis form: attention scratch, P slot");
+static_assert(2 * RES_POLL_WAVES <= RES_WAVES - 1, "a loading wave per polling wave, one for P");
 static_assert(SM_RQ >= 2 * (RES_LMAX + 32) + RES_LMAX + RES_WAVES, "general attention form: weights, energies");
 static_assert(SM_RM >= 2 * 6 * 64 * 4 + RES_LMAX + 32, "general attention form: cumulative weights");
 static_assert(HDEC >= 4 * RES_LMAX, "full evaluation: four waves' partials in xh_dec");
@@ -225,8 +233,10 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
     float* an = abuf + 2 * RES_LMAX;  // unnormalised forward weights of this step
     float* scr = an + RES_LMAX;       // [2 * RES_WAVES] + candidate values [16]
     float* xv = scr + 2 * RES_WAVES + 16;
+    float* xpt = xv + ADIM;             // [64] wave 0's P values of the step, loaded by wave 6
     long long* pacc = reinterpret_cast<long long*>(rm + SM_RM);
     float* xp1 = rm + SM_RM + SM_PROF;  // pre1_t (prenet layer 1 output) gathered by wave 0
+    float* xrow = xp1 + PRE;            // [SM_OPR] the entering encoder row, channels of waves 0-2, loaded by waves 3-5
     // general attention form (every CU): attention weights of the last two steps, zero-padded by
     // 16 on both sides for the location convolution ([2][GW_PAD], position j at j + 16), the
     // gathered energies, the transition agent's wave partials; the cumulative weights (padded)
@@ -359,6 +369,9 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
     if (prof && tid == 0) plast = (long long)wall_clock64();
     int n = 0, n_prev = 0;
     float ufa = 0.f, vb = 0.f, ex = 0.f, erow[4] = {0.f, 0.f, 0.f, 0.f}, ptc = 0.f;
+    // synthesis form, step 12: the entering row's own channel (waves 3-7) and the channel of waves
+    // 0-2 (waves 3-5), P at the candidate positions (wave 6)
+    float op_own = 0.f, op_row = 0.f, op_pt = 0.f;
     // (volatile buffer loads: the compiler may not sink them past the volatile polls of the h_att
     // gather to their use in the context, where their latency would sit on the critical path)
     const auto renc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.enc), (short)0, L * ENC * 4, 0x00020000);
@@ -371,23 +384,6 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         for (int k = 0; k < 4; ++k)
             erow[k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
                 renc, clo + k <= chi ? ((clo + k) * ENC + tid) * 4 : OOB_OFF, 0, VOLATILE_AUX));
-    };
-    // The rows for the step after one whose argmax was `from`: the window follows the argmax, which
-    // the forward attention moves by at most one position on most steps, so the registers already
-    // hold it (no load) or all but its last row (one load, the others shift down; a row past L-1
-    // reads 0 either way).  Four or five loads fewer ahead of the h_att poll (vmcnt is in order).
-    auto advance_rows = [&](int from, int nn) {
-        if (nn == from) return;
-        if (nn == from + 1 && from >= 1) {
-            ex = erow[0];
-            erow[0] = erow[1];
-            erow[1] = erow[2];
-            erow[2] = erow[3];
-            erow[3] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-                renc, nn + 2 <= L - 1 ? ((nn + 2) * ENC + tid) * 4 : OOB_OFF, 0, VOLATILE_AUX));
-        } else {
-            prefetch_rows(nn);
-        }
     };
     if constexpr (!GEN) {  // synthesis form: every CU runs the attention step
         n = a.nidx[0];
@@ -617,6 +613,14 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         for (int i = 0; i < 2; ++i) acc_a = dot4(wa[i], ld4(xpre + i * 128 + ks * 4), acc_a);
         acc_a = sum32_dpp(acc_a);
         if (ks == 31) gates[r] = acc_a;
+        if constexpr (!GEN) {
+            // the operands waves 3-6 loaded at the end of step t-1 (step 12: two XCD-local edges
+            // ago): to LDS for waves 0-2, which read them after B2
+            if (t > 0) {
+                if (wave >= RES_POLL_WAVES && wave < 2 * RES_POLL_WAVES) xrow[tid - 64 * RES_POLL_WAVES] = op_row;
+                if (wave == 2 * RES_POLL_WAVES) xpt[lane] = op_pt;
+            }
+        }
         __syncthreads();  // B2
         RES_MARK(3);
         if (tid < 16) {
@@ -631,17 +635,33 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         }
         // 4) gather h_att_t (all waves); first wave 4 writes the mel row c of step t-1 (xh_dec, xctx
         //    still hold h_dec_{t-1}, ctx_{t-1}): off the critical path of step t-1's pre1 rows.  The
-        //    synthesis form first issues this step's attention operands (the encoder row the mask can
-        //    keep that the CU does not hold yet; wave 0: P of its four dims at the 16 candidate
-        //    positions, one load per lane): in flight while h_att is awaited (a load issued
-        //    before the pre1 poll instead held that poll up by its latency, vmcnt being in order, and
-        //    with it the XCD's prenet-2 rows: 1.2 us per step, round-4 trace)
-        if (!GEN && t > 0) {
-            advance_rows(n_prev, n);
-            if (wave == 0) {  // lane (m = lane / 16, slot = lane % 16): P[rank + 32 m][pos_slot]
-                const int pos = res_candidate(lane & 15, n, n_prev, L);
-                ptc = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
-                    rpt, pos >= 0 ? ((rank + 32 * (lane >> 4)) * a.Lcap + pos) * 4 : OOB_OFF, 0, VOLATILE_AUX));
+        //    synthesis form's attention operands of this step (the encoder row the mask can keep
+        //    that the CU does not hold yet; wave 0: P of its four dims at the 16 candidate positions)
+        //    were issued at the end of step t-1 by waves 3-7 (step 12).  A load issued ahead of a
+        //    poll holds the poll up by its own latency, vmcnt being in order: ahead of this poll it
+        //    cost 0.3 us of the h_att edge on every CU, ahead of the pre1 poll 1.2 us per step
+        //    (round-4 trace)
+        if constexpr (!GEN) {
+            // The window follows the argmax, which the forward attention moves by at most one position
+            // on most steps: the registers already hold it (nothing to do) or all but its last row
+            // (the others shift down, the entering row arrives: waves 3-7 loaded their channel at the
+            // end of step t-1, the polling waves take theirs from LDS, written ahead of B2 by waves
+            // 3-5): no load ahead of this poll.  A window that is reloaded whole (the argmax wrapped
+            // or moved by more than one: rare, and five rows do not fit the free LDS) is still
+            // loaded here, by every wave.  (The early loads have one definition each, op_*: loaded
+            // straight into ex / erow, the step's end waits for them to copy registers.)
+            if (t > 0) {
+                if (n == n_prev + 1 && n_prev >= 1) {
+                    ex = erow[0];
+                    erow[0] = erow[1];
+                    erow[1] = erow[2];
+                    erow[2] = erow[3];
+                    if (wave < RES_POLL_WAVES) erow[3] = xrow[tid];
+                    else erow[3] = op_own;
+                } else if (n != n_prev) {
+                    prefetch_rows(n);
+                }
+                if (wave == 0) ptc = xpt[lane];
             }
         }
         {
@@ -1134,7 +1154,7 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         if (flags[1]) break;
         if constexpr (!GEN) {
             n_prev = n;
-            n = flags[6];  // argmax(prev_alpha) of the next step (its loads: h_att wait)
+            n = flags[6];  // argmax(prev_alpha) of the next step (its loads: step 12)
         }
         if constexpr (GEN) {
             if (gf & GEN_TA) {
@@ -1205,6 +1225,35 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
             }
         }
         if (prof && tid == 128) pacc[13] += (long long)wall_clock64() - m0;
+        // 12) synthesis form: step t+1's attention operands, issued by the waves that do not poll
+        //     before its h_att gather (3-7), behind their prenet-1 row: in flight during the pre1
+        //     and prenet-2 edges (these waves use them ahead of B2; their next poll is the h_att
+        //     gather).  When the window moves on by one: waves 3-7 their own channel of the
+        //     entering encoder row (a row past L-1 reads 0), waves 3-5 also the channel of waves
+        //     0-2 (tid - 192); on every step wave 6: P of the CU's four dims at the 16 candidate
+        //     positions, lane (m = lane / 16, slot = lane % 16): P[rank + 32 m][pos_slot].  What
+        //     waves 0-2 need goes to LDS ahead of B2.  (Written right after P1, 0.8 us after the
+        //     issue, it waited for the loads on the step's chain: 0.6 % of a sentence.  Issued
+        //     after P1 of the same step, 1 us ahead of B2, they cost 2 %: the entering row is new
+        //     to the XCD's L2.)  A step that never runs leaves them unused (every offset lies
+        //     inside its buffer or at OOB_OFF).
+        if constexpr (!GEN) {
+            if (wave >= RES_POLL_WAVES) {
+                if (n == n_prev + 1 && n_prev >= 1) {
+                    const int ro = n + 2 <= L - 1 ? ((n + 2) * ENC + tid) * 4 : OOB_OFF;
+                    op_own = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(renc, ro, 0, VOLATILE_AUX));
+                    if (wave < 2 * RES_POLL_WAVES)
+                        op_row = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+                            renc, n + 2 <= L - 1 ? ro - 256 * RES_POLL_WAVES : OOB_OFF, 0, VOLATILE_AUX));
+                }
+                if (wave == 2 * RES_POLL_WAVES) {
+                    const int pos = res_candidate(lane & 15, n, n_prev, L);
+                    op_pt = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+                        rpt, pos >= 0 ? ((rank + 32 * (lane >> 4)) * a.Lcap + pos) * 4 : OOB_OFF, 0, VOLATILE_AUX));
+                    if (lane == 0) { RES_EV(t, 14) }
+                }
+            }
+        }
     }
     if (flags[1]) return;
     if (wave == 4 && t > 0) mel_row(t - 1);  // the last step's mel row (its h_att gather never came)
