@@ -196,9 +196,20 @@ tts_status tts_decoder_profile(tts_decoder* d, int reps, float* kernel_ms, int n
 tts_status tts_postnet_create(const tts_tensor* tensors, int n_tensors, int n_mel, void* stream,
                               tts_postnet** out);
 void tts_postnet_destroy(tts_postnet* p);
-/*   mel [dev] fp32 [B][Tmax][n_mel] time-major; T [host] int32 [B]; out [dev] same shape. */
+/*   mel [dev] fp32 [B][Tmax][n_mel] time-major; T [host] int32 [B]; out [dev] same shape.
+ * Rows t >= T[b] of mel are never read and may hold anything (NaN included); rows t >= T[b] of
+ * out are never written (they keep what the caller put there).  T[b] = 0 is legal: that sentence
+ * is neither read nor written.  Tmax may exceed the longest T[b]. */
 tts_status tts_postnet_run(tts_postnet* p, const float* mel, const int32_t* T, int B, int Tmax,
                            float* out, void* stream);
+/* Which convolution kernel served each of the five layers of the last tts_postnet_run (no
+ * reference counterpart): kinds[0..4], n >= 5, -1 before the first run.  0 small-batch kernel
+ * with channel-major weights, 1 small-batch tap-major with 32 output channels per workgroup,
+ * 2 the same with 16, 3 tiled with 16-frame tiles, 4 split-K plus a reduce launch, 5 split-K
+ * reducing in the same launch (TTS_CONV_FUSED_REDUCE=1), 6 variable-length 64-frame tiles,
+ * 7 tiled 32-frame, 8 tiled 64-frame.  The host chooses by sum T[b], B * ceil(max T[b] / 16),
+ * the layer's channels and TTS_CONV_VL. */
+tts_status tts_postnet_last_path(tts_postnet* p, int* kinds, int n);
 
 /* Audio parameters of AudioProcessor (utils/audio.py:12-54, 114-119). */
 typedef struct tts_audio_config {
@@ -433,7 +444,8 @@ tts_status tts_tacotron_decode_teacher(tts_tacotron* t, const float* enc, const 
 
 /* Replaces PostCBHG + last_linear + sigmoid (layers/tacotron.py:246-259, models/tacotrongst.py:43-45,
  * 77-78): mel [dev] fp32 [B][Tmax][80], T [host] int32 [B] -> linear [dev] fp32 [B][Tmax][1025]
- * (rows past T[b] zero). */
+ * (rows past T[b] zero).  Rows t >= T[b] of mel are never read and may hold anything (NaN
+ * included); T[b] = 0 is legal and Tmax may exceed the longest T[b]. */
 tts_status tts_tacotron_postnet(tts_tacotron* t, const float* mel, const int32_t* T, int B, int Tmax,
                                 float* linear, void* stream);
 

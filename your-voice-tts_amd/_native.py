@@ -29,7 +29,7 @@ EXPORTS = (
     "tts_decoder_create", "tts_decoder_destroy", "tts_decoder_run", "tts_decoder_run_continue", "tts_decoder_run_teacher",
     "tts_decoder_last_timing", "tts_decoder_last_path", "tts_decoder_resident_limits", "tts_decoder_resident_phases", "tts_decoder_resident_trace",
     "tts_decoder_profile",
-    "tts_postnet_create", "tts_postnet_destroy", "tts_postnet_run",
+    "tts_postnet_create", "tts_postnet_destroy", "tts_postnet_run", "tts_postnet_last_path",
     "tts_gl_create", "tts_gl_destroy", "tts_gl_run", "tts_gl_last_timing", "tts_gl_last_path", "tts_gl_profile",
     "tts_gl_set_mel_basis", "tts_gl_melspectrogram", "tts_gl_set_phase_state", "tts_gl_get_phase_state",
     "tts_gl_draw_phases", "tts_gl_save_pcm16", "tts_gl_analyze", "tts_gl_linear_to_mel",
@@ -104,6 +104,7 @@ def _declare(lib):
     lib.tts_postnet_destroy.argtypes = [vp]
     lib.tts_postnet_destroy.restype = None
     lib.tts_postnet_run.argtypes = [vp, vp, I32P, ctypes.c_int, ctypes.c_int, vp, vp]
+    lib.tts_postnet_last_path.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
     lib.tts_gl_create.argtypes = [ctypes.POINTER(AudioConfig), vp, vp, ctypes.POINTER(vp)]
     lib.tts_gl_destroy.argtypes = [vp]
     lib.tts_gl_destroy.restype = None

@@ -77,8 +77,22 @@ hipError_t copy_strided(const float* src, int n, float* dst, int stride, hipStre
 // scale = gamma / sqrt(var + eps); shift = beta + (bias - mean) * scale (bias may be null)
 hipError_t fold_bn(const float* bias, const float* gamma, const float* beta, const float* mean, const float* var,
                    int C, float eps, float* scale, float* shift, hipStream_t s);
+// The kernel conv_launch chose for a launch (conv1d.hip launch_kw / launch_small), for the callers'
+// *_last_path queries and the contract tests; the values are part of tts_postnet_last_path's ABI.
+enum ConvKind {
+    CONV_KIND_SMALL_CM = 0,       // conv_small_kernel, channel-major K (Cin != 512)
+    CONV_KIND_SMALL_TAP32 = 1,    // conv_small_kernel, tap-major, 32 output channels per workgroup
+    CONV_KIND_SMALL_TAP16 = 2,    // conv_small_kernel, tap-major, 16 output channels per workgroup
+    CONV_KIND_TILED16 = 3,        // conv_kernel, 16-frame tiles
+    CONV_KIND_SPLITK_REDUCE = 4,  // split-K conv_kernel + conv_reduce_kernel
+    CONV_KIND_SPLITK_FUSED = 5,   // split-K conv_kernel reducing its own partials (TTS_CONV_FUSED_REDUCE=1)
+    CONV_KIND_VARLEN64 = 6,       // conv_vl_kernel, 64-frame tiles over the packed frame axis
+    CONV_KIND_TILED32 = 7,        // conv_kernel, 32-frame tiles (KW = 5)
+    CONV_KIND_TILED64 = 8,        // conv_kernel, 64-frame tiles (KW = 1 / 3 / 8 / 16)
+};
 // KW in {1, 3, 5, 8, 16}; Cin must be a multiple of the K step (16 for KW <= 5, 8 for KW = 8, 4 for
-// KW = 16).  frames_hint = sum of T_b picks the tile height (small batches: 16 frames).
-hipError_t conv_launch(const ConvArgs& a, int KW, int B, int frames_hint, hipStream_t s);
+// KW = 16).  frames_hint = sum of T_b picks the tile height (small batches: 16 frames).  `kind`, if
+// given, receives the ConvKind of the kernel launched.
+hipError_t conv_launch(const ConvArgs& a, int KW, int B, int frames_hint, hipStream_t s, int* kind = nullptr);
 
 }  // namespace tts

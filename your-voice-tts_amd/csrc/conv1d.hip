@@ -639,7 +639,7 @@ __global__ __launch_bounds__(CS_THREADS) void conv_small_kernel(const ConvArgs a
 }
 
 template <int KW>
-bool launch_small(const ConvArgs& a, int B, int frames_hint, hipStream_t s, hipError_t* err) {
+bool launch_small(const ConvArgs& a, int B, int frames_hint, hipStream_t s, hipError_t* err, int* kind) {
     static const int limit = getenv("TTS_CONV_SMALL") ? atoi(getenv("TTS_CONV_SMALL")) : 1024;  // frames; 0 = off
     if (!a.Wf || frames_hint > limit || a.pool2 || a.act == CONV_HIGHWAY || (a.Cin & 3) || a.Cin > 512 ||
         (a.co_pad % CS_BN) || ((a.Cin * KW) & 7))
@@ -650,14 +650,18 @@ bool launch_small(const ConvArgs& a, int B, int frames_hint, hipStream_t s, hipE
     const dim3 grid(tiles * (a.co_pad / CS_BN));
     // 16-channel tiles while the 32-channel grid leaves CUs idle (TTS_CONV_N16: that grid bound)
     static const int n16_max = getenv("TTS_CONV_N16") ? atoi(getenv("TTS_CONV_N16")) : 128;
-    if (a.wf_tap && a.Cin == CS_TAP_CIN && a.Wf16 && (int)grid.x <= n16_max)
+    if (a.wf_tap && a.Cin == CS_TAP_CIN && a.Wf16 && (int)grid.x <= n16_max) {
         hipLaunchKernelGGL((conv_small_kernel<KW, true, true>), dim3(tiles * (a.co_pad / 16)), dim3(CS_THREADS), smem, s, a);
-    else if (a.wf_tap && a.Cin == CS_TAP_CIN)
+        *kind = CONV_KIND_SMALL_TAP16;
+    } else if (a.wf_tap && a.Cin == CS_TAP_CIN) {
         hipLaunchKernelGGL((conv_small_kernel<KW, true, false>), grid, dim3(CS_THREADS), smem, s, a);
-    else if (a.wf_tap)
+        *kind = CONV_KIND_SMALL_TAP32;
+    } else if (a.wf_tap) {
         return false;  // (tap-major weights for another Cin: never packed so, conv_pack_frag_tap refuses)
-    else
+    } else {
         hipLaunchKernelGGL((conv_small_kernel<KW, false, false>), grid, dim3(CS_THREADS), smem, s, a);
+        *kind = CONV_KIND_SMALL_CM;
+    }
     *err = hipGetLastError();
     return true;
 }
@@ -775,11 +779,11 @@ __global__ void conv_reduce_kernel(const ConvArgs a, int B, int nsplit) {
 }
 
 template <int KW>
-hipError_t launch_kw(const ConvArgs& a, int B, int frames_hint, hipStream_t s) {
+hipError_t launch_kw(const ConvArgs& a, int B, int frames_hint, hipStream_t s, int* kind) {
     const dim3 block(256);
     if constexpr (KW == 1 || KW == 5) {
         hipError_t e = hipSuccess;
-        if (launch_small<KW>(a, B, frames_hint, s, &e)) return e;
+        if (launch_small<KW>(a, B, frames_hint, s, &e, kind)) return e;
     }
     constexpr int BK = KW <= 5 ? 16 : (KW <= 8 ? 8 : 4);
     const int Tt = a.Ttile ? a.Ttile : a.Tmax;
@@ -802,6 +806,7 @@ hipError_t launch_kw(const ConvArgs& a, int B, int frames_hint, hipStream_t s) {
                 const int64_t total = (int64_t)B * Tt * a.Cout;
                 hipLaunchKernelGGL(conv_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a, B, ns);
             }
+            *kind = b.tickets ? CONV_KIND_SPLITK_FUSED : CONV_KIND_SPLITK_REDUCE;
             return hipGetLastError();
         }
     }
@@ -811,20 +816,24 @@ hipError_t launch_kw(const ConvArgs& a, int B, int frames_hint, hipStream_t s) {
         Tt < 65536 - 4 && B * (Tt + 4) < (1 << 30) / 64) {
         const int vtiles = (B * (Tt + 2 * ((KW - 1) / 2)) + 63) / 64;  // upper bound: tiles past the end exit
         hipLaunchKernelGGL(conv_vl_kernel<5>, dim3((unsigned)(vtiles * (a.co_pad / CONV_BN))), block, 0, s, a, B);
+        *kind = CONV_KIND_VARLEN64;
         return hipGetLastError();
     }
     if (frames_hint <= 4096) {
         const dim3 grid(((Tt + 15) / 16) * (a.co_pad / CONV_BN) * B);
         hipLaunchKernelGGL((conv_kernel<KW, 16, 1, 4>), grid, block, 0, s, a);
+        *kind = CONV_KIND_TILED16;
     } else if (KW == 5) {
         // the Tacotron2 encoder / postnet convs (sentences of 60-1000 frames): 32-frame tiles halve
         // the last tile's padding rows; measured -0.3 ms per configs[2] batch (the KW 1 / 3 / 8 / 16
         // CBHG launches of configs[4] measured slower with them and keep 64)
         const dim3 grid(((Tt + 31) / 32) * (a.co_pad / CONV_BN) * B);
         hipLaunchKernelGGL((conv_kernel<KW, 32, 2, 2>), grid, block, 0, s, a);
+        *kind = CONV_KIND_TILED32;
     } else {
         const dim3 grid(((Tt + 63) / 64) * (a.co_pad / CONV_BN) * B);
         hipLaunchKernelGGL((conv_kernel<KW, 64, 2, 2>), grid, block, 0, s, a);
+        *kind = CONV_KIND_TILED64;
     }
     return hipGetLastError();
 }
@@ -895,15 +904,17 @@ hipError_t fold_bn(const float* bias, const float* gamma, const float* beta, con
     return hipGetLastError();
 }
 
-hipError_t conv_launch(const ConvArgs& a, int KW, int B, int frames_hint, hipStream_t s) {
+hipError_t conv_launch(const ConvArgs& a, int KW, int B, int frames_hint, hipStream_t s, int* kind) {
     const int bk = KW <= 5 ? 16 : (KW <= 8 ? 8 : 4);
     if (a.Cin % bk || (a.act == CONV_HIGHWAY && (a.Cout & 1))) return hipErrorInvalidValue;
+    int unused;
+    if (!kind) kind = &unused;
     switch (KW) {
-        case 1: return launch_kw<1>(a, B, frames_hint, s);
-        case 3: return launch_kw<3>(a, B, frames_hint, s);
-        case 5: return launch_kw<5>(a, B, frames_hint, s);
-        case 8: return launch_kw<8>(a, B, frames_hint, s);
-        case 16: return launch_kw<16>(a, B, frames_hint, s);
+        case 1: return launch_kw<1>(a, B, frames_hint, s, kind);
+        case 3: return launch_kw<3>(a, B, frames_hint, s, kind);
+        case 5: return launch_kw<5>(a, B, frames_hint, s, kind);
+        case 8: return launch_kw<8>(a, B, frames_hint, s, kind);
+        case 16: return launch_kw<16>(a, B, frames_hint, s, kind);
         default: return hipErrorInvalidValue;
     }
 }

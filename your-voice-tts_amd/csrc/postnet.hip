@@ -25,6 +25,7 @@ struct tts_postnet {
     int* T = nullptr;
     int Tcap_B = 0;
     float* part = nullptr;  // split-K workspace (CONV_SPLITK_FLOATS)
+    int last_kind[5] = {-1, -1, -1, -1, -1};  // ConvKind per layer of the last run (tts_postnet_last_path)
 };
 
 extern "C" {
@@ -107,6 +108,12 @@ tts_status tts_postnet_run(tts_postnet* p, const float* mel, const int32_t* T, i
     return tts::postnet_run_dev(p, mel, 0, nullptr, 1, T, B, Tmax, out, static_cast<hipStream_t>(stream));
 }
 
+tts_status tts_postnet_last_path(tts_postnet* p, int* kinds, int n) {
+    TTS_CHECK(p && kinds && n >= 5, TTS_ERR_INVALID, "tts_postnet_last_path needs room for 5 kinds");
+    for (int l = 0; l < 5; ++l) kinds[l] = p->last_kind[l];
+    return TTS_OK;
+}
+
 }  // extern "C"
 
 namespace tts {
@@ -174,7 +181,7 @@ tts_status postnet_run_dev(tts_postnet* p, const float* mel, int mel_tmax, const
         a.part = p->part;
         a.tickets = reinterpret_cast<int*>(p->part + CONV_SPLITK_FLOATS);
         a.Ttile = Tlong;
-        TTS_HIP(conv_launch(a, 5, B, frames, s));
+        TTS_HIP(conv_launch(a, 5, B, frames, s, &p->last_kind[l]));
         if (pad_kernel()) hipLaunchKernelGGL(postnet_pad_kernel, dim3(1), dim3(64), 0, s);  // measurement only
         in = a.out;
     }
