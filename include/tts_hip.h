@@ -302,6 +302,33 @@ tts_status tts_gl_find_endpoint(tts_gl* g, const double* wav, int64_t pitch, con
 tts_status tts_gl_take_segments(tts_gl* g, const double* src, int64_t src_pitch, const int32_t* start,
                                 const int32_t* len, int B, double* dst, int64_t dst_pitch, void* stream);
 
+/* The interpolation filter of the resampler below (utils/audio.py:239: librosa.load resamples with resampy's
+ * "kaiser_best"): the right half of a windowed sinc, num_table entries per zero crossing, as
+ * resampy.filters.sinc_window returns it (kaiser_best: n_win 32 769, num_table 512).  Copied to the device;
+ * replaces the handle's previous filter.  INVALID: a null pointer, a non-positive n_win or num_table.
+ *   half_win [host] fp64 [n_win] */
+tts_status tts_gl_set_resample_filter(tts_gl* g, const double* half_win, int n_win, int num_table);
+
+/* librosa.load's resampler (utils/audio.py:239; librosa 0.6.2 resample with fix=True, resampy 0.2.x resample_f)
+ * for a ragged batch on the device, one launch: sentence b goes from orig_sr[b] to target_sr.  With
+ * ratio = target_sr / orig_sr[b] it has n_res = int(N[b] * ratio) outputs and n_fix = ceil(N[b] * ratio)
+ * samples (fix_length; those at and beyond n_res are zero).  Every source value is rounded to float32 on load
+ * (librosa hands resampy float32), the accumulator of an output is float32, every tap is one fp64 multiply,
+ * one fp64 add and one rounding to float32 in resampy's order, and the time register is resampy's serial
+ * float64 sum (built on the host once per rate pair, cached on the handle): the result equals resampy's bit
+ * for bit, each value a float32.  A sentence with orig_sr[b] == target_sr passes through.  No sample at or
+ * beyond N[b] is read; dst is zero from n_res to dst_pitch, so it feeds tts_gl_trim_silence,
+ * tts_gl_take_segments and tts_gl_analyze as it is.  n_out receives n_fix.
+ * INVALID before any launch: a null pointer, B <= 0, a non-positive rate, N[b] outside [1, src_pitch],
+ * n_res < 1, n_fix > dst_pitch, no filter set, step = int(min(1, ratio) * num_table) < 1, wings longer than
+ * the 16 384 inputs a workgroup stages (kaiser_best: a ratio below 5 / 512): the error text names the
+ * sentence.  Waits for the stream before it returns.
+ *   src [dev] fp64 [B][src_pitch]; N, orig_sr [host] int32 [B]; dst [dev] fp64 [B][dst_pitch];
+ *   n_out [host] int32 [B] */
+tts_status tts_gl_resample(tts_gl* g, const double* src, int64_t src_pitch, const int32_t* N,
+                           const int32_t* orig_sr, int target_sr, int B, double* dst, int64_t dst_pitch,
+                           int32_t* n_out, void* stream);
+
 /* Mel analysis for GST style wavs: AudioProcessor.melspectrogram (utils/audio.py:146-152) as used by
  * compute_style_mel (utils/synthesis.py:28-35): pre-emphasis FIR, librosa 0.6.2 stft (float64 FFT,
  * complex64 result), |D|, mel projection (float64), amp->dB, _normalize.

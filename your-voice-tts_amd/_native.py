@@ -34,6 +34,7 @@ EXPORTS = (
     "tts_gl_set_mel_basis", "tts_gl_melspectrogram", "tts_gl_set_phase_state", "tts_gl_get_phase_state",
     "tts_gl_draw_phases", "tts_gl_save_pcm16", "tts_gl_analyze", "tts_gl_linear_to_mel",
     "tts_gl_trim_silence", "tts_gl_find_endpoint", "tts_gl_take_segments",
+    "tts_gl_set_resample_filter", "tts_gl_resample",
     "tts_synth_create", "tts_synth_destroy", "tts_synth_run", "tts_synth_sync",
     "tts_tacotron_create", "tts_tacotron_destroy", "tts_tacotron_encode", "tts_tacotron_decode",
     "tts_tacotron_decode_teacher",
@@ -126,6 +127,9 @@ def _declare(lib):
     lib.tts_gl_find_endpoint.argtypes = [vp, vp, ctypes.c_int64, I32P, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_double, I32P, vp]
     lib.tts_gl_take_segments.argtypes = [vp, vp, ctypes.c_int64, I32P, I32P, ctypes.c_int, vp, ctypes.c_int64, vp]
+    lib.tts_gl_set_resample_filter.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int]
+    lib.tts_gl_resample.argtypes = [vp, vp, ctypes.c_int64, I32P, I32P, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int64,
+                                    I32P, vp]
     lib.tts_synth_create.argtypes = [vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
     lib.tts_synth_destroy.argtypes = [vp]
     lib.tts_synth_destroy.restype = None
@@ -164,7 +168,7 @@ def _declare(lib):
         if name.endswith(("_create", "_run", "_timing", "_profile", "_encode", "_decode", "_postnet", "_state",
                           "_continue", "_basis", "_melspectrogram", "_path", "_sync", "_phases", "_teacher",
                           "_phase_state", "_pcm16", "_limits", "_analyze", "_to_mel", "_silence", "_endpoint",
-                          "_segments", "_masked", "_logits")):
+                          "_segments", "_masked", "_logits", "_filter", "_resample")):
             fn.restype = ctypes.c_int
 
 

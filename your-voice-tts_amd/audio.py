@@ -63,6 +63,32 @@ def mel_basis(sr, n_fft, n_mels, fmin=0.0, fmax=None):
     return w * (2.0 / (edges[2:] - edges[:-2]))[:, None]
 
 
+def resample_filter(res_type="kaiser_best"):
+    """resampy 0.2.x's interpolation filter by name: (half_win float64 [num_table * num_zeros + 1],
+    num_table).  "kaiser_best" is sinc_window(num_zeros=64, precision=9, kaiser(beta=14.769656459379492),
+    rolloff=0.9475937167399596), the filter librosa.load resamples with; no other name is built (a caller
+    may hand resample_batch its own (half_win, num_table) pair)."""
+    if res_type != "kaiser_best":
+        raise NotImplementedError("resample filter %r (only 'kaiser_best' is built)" % (res_type,))
+    num_zeros, precision, beta, rolloff = 64, 9, 14.769656459379492, 0.9475937167399596
+    num_table = 2 ** precision
+    n = num_table * num_zeros
+    sinc_win = rolloff * np.sinc(rolloff * np.linspace(0, num_zeros, num=n + 1, endpoint=True))
+    taper = scipy.signal.windows.kaiser(2 * n + 1, beta)[n:]
+    return taper * sinc_win, num_table
+
+
+def resample_lengths(N, orig_sr, target_sr):
+    """(n_res, n_fix) of N samples resampled from orig_sr to target_sr: resampy's output length
+    int(N * ratio) and librosa's fix_length int(ceil(N * ratio)); the result has n_fix samples, zero at and
+    beyond n_res.  ValueError when n_res < 1, as resampy raises."""
+    ratio = float(target_sr) / orig_sr
+    n_res = int(N * ratio)
+    if n_res < 1:
+        raise ValueError("Input signal length=%d is too small to resample from %s->%s" % (N, orig_sr, target_sr))
+    return n_res, int(np.ceil(N * ratio))
+
+
 class AudioProcessor:
     def __init__(self, sample_rate=None, num_mels=None, min_level_db=None, frame_shift_ms=None,
                  frame_length_ms=None, ref_level_db=None, num_freq=None, power=None, preemphasis=None,
@@ -88,6 +114,7 @@ class AudioProcessor:
         self.n_fft, self.hop_length, self.win_length = self._stft_parameters()
         self._gl = None
         self._mel_basis_set = False
+        self._resample_filter = None  # the named resample filter the handle holds (None: none, or a caller's table)
 
     def _stft_parameters(self):  # utils/audio.py:114-119
         n_fft = (self.num_freq - 1) * 2
@@ -417,9 +444,35 @@ class AudioProcessor:
             x = x.astype(np.float64)
         return file_sr, x
 
+    @staticmethod
+    def _to_mono_f32(x):
+        """librosa.load's conversion of _read_wav's samples ([N] or [N, C]): float32, then to_mono's mean
+        over the channels (float32 sum in channel order, divided by C)."""
+        x = np.asarray(x, dtype=np.float32)
+        if x.ndim == 1:
+            return x
+        acc = x[:, 0].copy()
+        for c in range(1, x.shape[1]):
+            acc = acc + x[:, c]
+        return acc / np.float32(x.shape[1])
+
     def load_wav(self, filename, sr=None):
-        """utils/audio.py:235-246 with soundfile's float64 conversion (PCM / 2**(bits-1))."""
+        """utils/audio.py:235-246.  Without ``sr``: soundfile's float64 conversion (PCM / 2**(bits-1)).
+        With ``sr`` (utils/audio.py:239, librosa.load(filename, sr=sr)): float32 conversion, mono mix,
+        resampling to ``sr`` on the device (resample_batch, a batch of one), and a float32 ndarray out.
+        int16 files convert exactly; other sample widths are converted as _read_wav does and then rounded
+        to float32 (audioread's own handling of those widths is not reproduced).  Trimming after a resample
+        runs the float64 trim_silence on the float32-valued samples; librosa's float32 arithmetic inside
+        effects.trim is not reproduced."""
         file_sr, x = self._read_wav(filename)
+        if sr is not None:
+            x = self._to_mono_f32(x)
+            wav, n = self.resample_batch(torch.from_numpy(x.astype(np.float64)).cuda()[None], [len(x)], file_sr, sr)
+            x = wav[0, :n[0]].cpu().numpy().astype(np.float32)
+            if self.do_trim_silence:
+                x = self.trim_silence(x.astype(np.float64)).astype(np.float32)
+            assert self.sample_rate == sr, "%s vs %s" % (self.sample_rate, sr)
+            return x
         if self.do_trim_silence:
             x = self.trim_silence(x)
         assert self.sample_rate == file_sr, "%s vs %s" % (self.sample_rate, file_sr)
@@ -485,23 +538,69 @@ class AudioProcessor:
                                                _native.stream_handle()), "tts_gl_take_segments")
         return out[:, :max(int(n) for n in lens)]
 
-    def load_wav_batch(self, filenames):
+    # ---------------------------------------------------------------- resampling (device)
+    def _set_resample_filter(self, res_type):
+        lib, h = self._handle()
+        if isinstance(res_type, str) and self._resample_filter == res_type:
+            return lib, h
+        half_win, num_table = resample_filter(res_type) if isinstance(res_type, str) else res_type
+        half_win = np.ascontiguousarray(half_win, dtype=np.float64)
+        self._resample_filter = None
+        _native.check(lib.tts_gl_set_resample_filter(h, half_win.ctypes.data_as(ctypes.c_void_p), len(half_win),
+                                                     int(num_table)), "tts_gl_set_resample_filter")
+        if isinstance(res_type, str):
+            self._resample_filter = res_type
+        return lib, h
+
+    def resample_batch(self, wav, N, orig_sr, target_sr=None, res_type="kaiser_best"):
+        """librosa 0.6.2 resample(y, orig_sr, target_sr, res_type, fix=True) of every sentence of the CUDA
+        float64 [B, Nmax] ``wav`` (N: samples per sentence) on the device (tts_gl_resample): resampy's
+        resample_f with a float32 accumulator, then fix_length.  orig_sr: one rate or one per sentence;
+        target_sr: default the processor's rate; res_type: "kaiser_best" or a (half_win, num_table) pair.
+        Samples are rounded to float32 on load and every result is a float32 value; a sentence already at
+        target_sr passes through.  Returns (CUDA float64 [B, max n_fix], n_fix per sentence); samples at
+        and beyond a sentence's n_res are zero."""
+        lib, h = self._set_resample_filter(res_type)
+        wav = self._wav_batch(wav)
+        B = len(N)
+        rates = [int(orig_sr)] * B if np.ndim(orig_sr) == 0 else [int(r) for r in orig_sr]
+        assert len(rates) == B and wav.shape[0] == B
+        target_sr = int(self.sample_rate if target_sr is None else target_sr)
+        n_fix = [resample_lengths(int(n), r, target_sr)[1] for n, r in zip(N, rates)]
+        out = torch.empty(B, max(n_fix), dtype=torch.float64, device=wav.device)
+        n_out = (ctypes.c_int32 * B)()
+        _native.check(lib.tts_gl_resample(h, ctypes.c_void_p(wav.data_ptr()), wav.stride(0), _native.i32_array(N),
+                                          _native.i32_array(rates), target_sr, B, ctypes.c_void_p(out.data_ptr()),
+                                          out.stride(0), n_out, _native.stream_handle()), "tts_gl_resample")
+        assert list(n_out) == n_fix
+        return out, n_fix
+
+    def load_wav_batch(self, filenames, sr=None):
         """load_wav of every file, as one ragged batch on the device: the files are read and converted
         on the host as load_wav does, uploaded once, and with do_trim_silence trimmed on the device
         (trim_silence_batch, take_segments).  Returns (CUDA float64 [B, Nmax], samples per sentence),
         what features_batch / melspectrogram_batch take.  A file too short to trim is kept whole with
-        the reference's message (utils/audio.py:240-244)."""
+        the reference's message (utils/audio.py:240-244).  With ``sr`` the files may have any mix of
+        rates and channel counts: each is converted as load_wav(filename, sr) converts it, the batch is
+        resampled to ``sr`` on the device (resample_batch), then trimmed; every sample is a float32 value."""
         self._handle()  # raises without a GPU / library: no CPU fallback
-        xs = []
+        xs, rates = [], []
         for filename in filenames:
             file_sr, x = self._read_wav(filename)
-            assert self.sample_rate == file_sr, "%s vs %s" % (self.sample_rate, file_sr)
+            if sr is None:
+                assert self.sample_rate == file_sr, "%s vs %s" % (self.sample_rate, file_sr)
+            else:
+                x = self._to_mono_f32(x)
             xs.append(x)
+            rates.append(file_sr)
         N = [len(x) for x in xs]
         host = np.zeros((len(xs), max(N)), dtype=np.float64)
         for b, x in enumerate(xs):
             host[b, :N[b]] = x
         wav = torch.from_numpy(host).cuda()
+        if sr is not None:
+            wav, N = self.resample_batch(wav, N, rates, sr)
+            assert self.sample_rate == sr, "%s vs %s" % (self.sample_rate, sr)
         if not self.do_trim_silence:
             return wav, N
         trim = [b for b in range(len(xs)) if N[b] >= self._trim_min_samples()]

@@ -1,6 +1,7 @@
 // The Griffin-Lim / AudioProcessor handle (struct tts_gl), private to the files that implement
 // its entry points: gl_handle.hip (create, destroy), griffin_lim.hip (synthesis), audio_analysis.hip
-// (spectrogram, mel), phase_mt.hip (numpy-stream phases), wav_io.hip (PCM16 join), silence.hip.
+// (spectrogram, mel), phase_mt.hip (numpy-stream phases), wav_io.hip (PCM16 join), silence.hip,
+// resample.hip.
 #pragma once
 #include <map>
 #include <tuple>
@@ -91,6 +92,22 @@ struct MtWork {
 };
 void mt_work_free(MtWork* w);
 
+// resample.hip: resampy's time register of one (orig_sr, target_sr) pair, tr[0] = 0, tr[t] = fl(tr[t - 1] + inc),
+// summed serially on the host (grown on demand) and mirrored on the device
+struct RsRegister {
+    std::vector<double> host;
+    DeviceBuf<double> dev;
+    size_t uploaded = 0;  // leading values the device copy holds
+};
+// ... and one sentence of a resampling launch
+struct RsSent {
+    const double* tr;  // the pair's register on the device (null: pass-through)
+    double scale;      // min(1, ratio)
+    double mult;       // ratio when it is < 1, else 1: win[o] = half_win[o] * mult
+    int N, n_res, step;
+    int first;         // first workgroup of the sentence
+};
+
 }  // namespace tts
 
 struct tts_gl {
@@ -155,6 +172,13 @@ struct tts_gl {
     // tts_gl_take_segments: start / len per sentence ([dev], host copy kept for the upload)
     tts::DeviceBuf<int> seg;
     std::vector<int32_t> seg_h;
+    // tts_gl_set_resample_filter / tts_gl_resample: the half window ([dev]), the time registers by
+    // (orig_sr, target_sr), the sentences of the current call ([dev], host copy kept for the upload)
+    tts::DeviceBuf<double> rs_win;
+    int rs_nwin = 0, rs_table = 0;
+    std::map<std::pair<int, int>, tts::RsRegister> rs_reg;
+    tts::DeviceBuf<tts::RsSent> rs_sent;
+    std::vector<tts::RsSent> rs_sent_h;
 };
 
 namespace tts {

@@ -24,8 +24,11 @@ void tts_gl_destroy(tts_gl* g) {
                     (void*)g->y.p, (void*)g->F.p, (void*)g->basis, (void*)g->band, (void*)g->NS.p, (void*)g->flags.p,
                     (void*)g->pstatus, (void*)g->pgr.p, (void*)g->wt, (void*)g->winc, (void*)g->wssp,
                     (void*)g->mt_state, (void*)g->mt_phase.p, (void*)g->mt_F.p, (void*)g->pcm_peak,
-                    (void*)g->pcm_start.p, (void*)g->sil.p, (void*)g->seg.p})
+                    (void*)g->pcm_start.p, (void*)g->sil.p, (void*)g->seg.p, (void*)g->rs_win.p,
+                    (void*)g->rs_sent.p})
         if (p) (void)hipFree(p);
+    for (auto& kv : g->rs_reg)
+        if (kv.second.dev.p) (void)hipFree(kv.second.dev.p);
     if (g->host_status) (void)hipHostFree(g->host_status);
     for (hipEvent_t e : {g->ev_in, g->ev_out, g->ev_t0, g->ev_t1, g->ev_done, g->ev_mt})
         if (e) (void)hipEventDestroy(e);
