@@ -551,6 +551,78 @@ tts_status tts_loss_masked(tts_loss* l, int kind, const float* input, int64_t in
 tts_status tts_loss_bce_logits(tts_loss* l, const float* logits, const float* targets, int64_t n, double* sum_dev,
                                float* loss_dev, double* sum_out, double* loss_out, void* stream);
 
+/* ---------------------------------------------------------------- training update
+ * The tail of every training iteration (train.py:157-167) on parameters, gradients and Adam state that stay
+ * in HBM: the custom weight decay, clip_grad_norm_ and torch.optim.Adam.step (weight_decay = 0, no amsgrad),
+ * as one fp64 norm reduction (two launches, as tts_loss_masked) and one pass that reads p, g, m, v once and
+ * writes p, m, v once (g too when the clip scales it).  The forward and the backward stay the caller's torch.
+ * The handle carries the chunk map of the tensor sizes (one chunk = TTS_OPTIM_CHUNK elements of one tensor,
+ * one fp64 partial each), the device copy of the per-call table and its pinned host copies. */
+typedef struct tts_optim tts_optim;
+#define TTS_OPTIM_CHUNK 8192
+
+/* One tensor of a call.  All pointers [dev] fp32, contiguous, numel elements.
+ *   g     may be NULL (param.grad is None): the tensor does not count in the norm and is neither clipped nor
+ *         stepped, as torch skips it; the weight decay still applies (generic_utils.py:178-181 tests nothing)
+ *   m, v  exp_avg, exp_avg_sq; needed by tts_optim_adam and tts_optim_step only
+ *   step  the number of THIS update (torch's state["step"] after its increment, >= 1); per tensor, as a
+ *         tensor without a gradient does not advance; read by tts_optim_adam and tts_optim_step only */
+typedef struct tts_optim_tensor {
+    float* p;
+    float* g;
+    float* m;
+    float* v;
+    int64_t numel;
+    int64_t step;
+} tts_optim_tensor;
+
+tts_status tts_optim_create(tts_optim** out);
+void tts_optim_destroy(tts_optim* o);
+
+/* The sizes of the tensor set: builds the chunk map (host, then one upload; waits for the stream).  Calling
+ * it again with other sizes rebuilds it.  Every other call checks its table against these sizes.
+ * INVALID: a null pointer, n <= 0, an element count <= 0. */
+tts_status tts_optim_set_tensors(tts_optim* o, const int64_t* numel, int n, void* stream);
+
+/* The total gradient norm of clip_grad_norm_(parameters, max_norm) (generic_utils.py:158), nothing scaled.
+ *   norm64_dev [dev] fp64 [2] out: the sum of g * g over every element of every tensor with a gradient
+ *              (products and sums in fp64 from the fp32 operand, fixed order), and its square root
+ *   norm32_dev [dev] fp32 [2] out: the norm rounded once; the clip coefficient float(max_norm / (norm + 1e-6))
+ *              where that fp64 quotient is below 1, else exactly 1.0f (a NaN quotient stays NaN)
+ *   sumsq_out, norm_out [host] out, each may be NULL; if either is given the call waits for the stream
+ * The table goes up on the stream from pinned memory with every call.  INVALID before any launch, outputs
+ * untouched: a null handle, table or device output; n <= 0 or not the n of the sizes set; an element count
+ * <= 0 or not the one set; a null p; two entries with the same p; max_norm <= 0. */
+tts_status tts_optim_grad_norm(tts_optim* o, const tts_optim_tensor* t, int n, double max_norm, double* norm64_dev,
+                               float* norm32_dev, double* sumsq_out, double* norm_out, void* stream);
+
+/* Replaces torch.nn.utils.clip_grad_norm_ in check_update (generic_utils.py:155-162): tts_optim_grad_norm,
+ * then g <- g * coefficient in place where the coefficient is not 1.0f.  Arguments and checks as above. */
+tts_status tts_optim_clip(tts_optim* o, const tts_optim_tensor* t, int n, double max_norm, double* norm64_dev,
+                          float* norm32_dev, double* sumsq_out, double* norm_out, void* stream);
+
+/* Replaces weight_decay(optimizer, wd) (generic_utils.py:174-182): p <- p + float(-wd * lr) * p, in place, on
+ * every tensor (m, v, g are not read and may be NULL).  wd == 0 launches nothing.
+ * INVALID: the table checks above; lr <= 0. */
+tts_status tts_optim_decay(tts_optim* o, const tts_optim_tensor* t, int n, double lr, double wd, void* stream);
+
+/* Replaces optimizer.step() of torch.optim.Adam(lr, betas, eps, weight_decay=0) (train.py:160, 454-457) as
+ * torch/optim/adam.py::_single_tensor_adam computes it: m <- m + w1 (g - m); v <- v * beta2, v <- v + (w2 g) g;
+ * p <- p + (-(lr / bc1) m) / (sqrt(v) / sqrt(bc2) + eps), fp32, one rounding per operation, with
+ * w1 = 1 - beta1, w2 = 1 - beta2, bc = 1 - beta^step in double and each scalar rounded once.
+ * INVALID: the table checks above; a null m or v or a step < 1 on a tensor with a gradient; lr <= 0; a beta
+ * outside [0, 1); eps < 0. */
+tts_status tts_optim_adam(tts_optim* o, const tts_optim_tensor* t, int n, double lr, double beta1, double beta2,
+                          double eps, void* stream);
+
+/* The three of train.py:158-160 in one pass over the parameter set: the norm (two launches), then per
+ * element decay, clip, Adam in that order, the clip coefficient read from norm32_dev[1] on the device (the
+ * host waits for nothing).  Bitwise tts_optim_decay, tts_optim_clip, tts_optim_adam in sequence.
+ * INVALID: the union of their checks. */
+tts_status tts_optim_step(tts_optim* o, const tts_optim_tensor* t, int n, double lr, double beta1, double beta2,
+                          double eps, double wd, double max_norm, double* norm64_dev, float* norm32_dev,
+                          void* stream);
+
 const char* tts_last_error(void);
 const char* tts_version(void);
 

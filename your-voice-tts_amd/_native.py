@@ -16,6 +16,7 @@ TTS_GL_FROM_MEL = 0
 TTS_GL_FROM_LINEAR = 1
 TTS_LOSS_L1 = 0
 TTS_LOSS_MSE = 1
+TTS_OPTIM_CHUNK = 8192  # elements per chunk of work of csrc/optim.hip (include/tts_hip.h)
 GL_PATHS = {0: "unfused", 1: "fused", 2: "persistent"}  # TTS_GL_PATH_* (include/tts_hip.h)
 DECODER_STEP_KERNELS = ("prenet2", "att_lstm", "query", "attention", "dec_lstm", "mel_fused")
 GL_KERNELS = ("gl_iter", "gl_ola")
@@ -41,6 +42,8 @@ EXPORTS = (
     "tts_tacotron_postnet", "tts_tacotron_last_timing", "tts_tacotron_last_path", "tts_tacotron_resident_phases",
     "tts_tacotron_profile",
     "tts_loss_create", "tts_loss_destroy", "tts_loss_masked", "tts_loss_bce_logits",
+    "tts_optim_create", "tts_optim_destroy", "tts_optim_set_tensors", "tts_optim_grad_norm", "tts_optim_clip",
+    "tts_optim_decay", "tts_optim_adam", "tts_optim_step",
     "tts_last_error", "tts_version",
 )
 
@@ -59,6 +62,11 @@ class TacotronConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in (
         "r", "memory_size", "attn_norm", "forward_attn", "trans_agent", "forward_attn_mask", "location_attn",
         "windowing", "gst", "num_speakers", "max_batch", "max_len", "max_steps")]
+
+
+class OptimTensor(ctypes.Structure):  # tts_optim_tensor
+    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p),
+                ("numel", ctypes.c_int64), ("step", ctypes.c_int64)]
 
 
 class AudioConfig(ctypes.Structure):
@@ -161,6 +169,16 @@ def _declare(lib):
     lib.tts_loss_masked.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64, I32P, ctypes.c_int,
                                     ctypes.c_int, ctypes.c_int, vp, vp, DP, I64P, DP, vp]
     lib.tts_loss_bce_logits.argtypes = [vp, vp, vp, ctypes.c_int64, vp, vp, DP, DP, vp]
+    OT, D = ctypes.POINTER(OptimTensor), ctypes.c_double
+    lib.tts_optim_create.argtypes = [ctypes.POINTER(vp)]
+    lib.tts_optim_destroy.argtypes = [vp]
+    lib.tts_optim_destroy.restype = None
+    lib.tts_optim_set_tensors.argtypes = [vp, I64P, ctypes.c_int, vp]
+    lib.tts_optim_grad_norm.argtypes = [vp, OT, ctypes.c_int, D, vp, vp, DP, DP, vp]
+    lib.tts_optim_clip.argtypes = lib.tts_optim_grad_norm.argtypes
+    lib.tts_optim_decay.argtypes = [vp, OT, ctypes.c_int, D, D, vp]
+    lib.tts_optim_adam.argtypes = [vp, OT, ctypes.c_int, D, D, D, D, vp]
+    lib.tts_optim_step.argtypes = [vp, OT, ctypes.c_int, D, D, D, D, D, D, vp, vp, vp]
     lib.tts_last_error.restype = ctypes.c_char_p
     lib.tts_version.restype = ctypes.c_char_p
     for name in EXPORTS:
@@ -168,7 +186,8 @@ def _declare(lib):
         if name.endswith(("_create", "_run", "_timing", "_profile", "_encode", "_decode", "_postnet", "_state",
                           "_continue", "_basis", "_melspectrogram", "_path", "_sync", "_phases", "_teacher",
                           "_phase_state", "_pcm16", "_limits", "_analyze", "_to_mel", "_silence", "_endpoint",
-                          "_segments", "_masked", "_logits", "_filter", "_resample")):
+                          "_segments", "_masked", "_logits", "_filter", "_resample", "_tensors", "_grad_norm",
+                          "_clip", "_decay", "_adam", "_step")):
             fn.restype = ctypes.c_int
 
 

@@ -6,6 +6,10 @@ line continuations stripped, as utils/generic_utils.py:24-32).  ``setup_model`` 
 and the 2-argument call its callers make (``synthesize.py:93``, ``server/synthesizer.py:55``),
 which raises TypeError in the reference; ``c.num_speakers`` may be absent (it is absent from
 every reference config, generic_utils.py:278).
+
+The training helpers of the same file: ``weight_decay`` and ``check_update`` (generic_utils.py:155-182) run on
+the device through ``optim.decay_`` / ``optim.clip_`` (csrc/optim.hip) with the reference's signatures and
+return values; ``lr_decay``, ``NoamLR``, ``mk_decay`` and ``count_parameters`` are host arithmetic, restated.
 """
 from __future__ import annotations
 
@@ -44,6 +48,66 @@ def sequence_mask(sequence_length, max_len=None):  # utils/generic_utils.py:209-
         max_len = int(sequence_length.max())
     seq_range = torch.arange(0, max_len, device=sequence_length.device).long()
     return seq_range.unsqueeze(0) < sequence_length.unsqueeze(1)
+
+
+def check_update(model, grad_clip):  # utils/generic_utils.py:155-162
+    """``clip_grad_norm_`` in place on the device plus the reference's inf test: ``(grad_norm, skip_flag)``.
+    ``model`` is an ``nn.Module`` or an iterable of parameters; ``grad_norm`` is a 0-dim CUDA float32 tensor.
+    Waits for the device where the reference's ``np.isinf(grad_norm)`` does."""
+    import math
+    from . import optim
+    params = model.parameters() if hasattr(model, "parameters") else model
+    grad_norm, value = optim.clip_(params, grad_clip)
+    skip_flag = False
+    if math.isinf(value):
+        print(" | > Gradient is INF !!")
+        skip_flag = True
+    return grad_norm, skip_flag
+
+
+def lr_decay(init_lr, global_step, warmup_steps):  # utils/generic_utils.py:165-171
+    warmup_steps = float(warmup_steps)
+    step = global_step + 1.
+    return init_lr * warmup_steps**0.5 * min(step * warmup_steps**-1.5, step**-0.5)
+
+
+def weight_decay(optimizer, wd):  # utils/generic_utils.py:174-182
+    """The reference's custom weight decay, ``p <- p + (-wd * lr) * p`` on every parameter of every group, on
+    the device and in place (the reference binds a new tensor to ``param.data``).  ``optimizer`` is an
+    ``optim.Adam`` or any torch optimizer over CUDA float32 parameters.  Returns ``(optimizer, current_lr)``."""
+    from . import optim
+    for group in optimizer.param_groups:
+        current_lr = group['lr']
+        optim.decay_(group['params'], current_lr, wd)
+    return optimizer, current_lr
+
+
+def __getattr__(name):  # NoamLR subclasses a torch class: made on first use, importing this module stays cheap
+    if name != "NoamLR":
+        raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+    import torch
+
+    class NoamLR(torch.optim.lr_scheduler._LRScheduler):  # utils/generic_utils.py:185-196
+        def __init__(self, optimizer, warmup_steps=0.1, last_epoch=-1):
+            self.warmup_steps = float(warmup_steps)
+            super().__init__(optimizer, last_epoch)
+
+        def get_lr(self):
+            step = max(self.last_epoch, 1)
+            return [base_lr * self.warmup_steps**0.5 * min(step * self.warmup_steps**-1.5, step**-0.5)
+                    for base_lr in self.base_lrs]
+
+    globals()["NoamLR"] = NoamLR
+    return NoamLR
+
+
+def mk_decay(init_mk, max_epoch, n_epoch):  # utils/generic_utils.py:199-200
+    return init_mk * ((max_epoch - n_epoch) / max_epoch)
+
+
+def count_parameters(model):  # utils/generic_utils.py:203-205
+    r"""Count number of trainable parameters in a network"""
+    return sum(p.numel() for p in model.parameters() if p.requires_grad)
 
 
 def setup_model(num_chars, num_speakers_or_c, c=None, **kw):
