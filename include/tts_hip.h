@@ -551,6 +551,34 @@ tts_status tts_loss_masked(tts_loss* l, int kind, const float* input, int64_t in
 tts_status tts_loss_bce_logits(tts_loss* l, const float* logits, const float* targets, int64_t n, double* sum_dev,
                                float* loss_dev, double* sum_out, double* loss_out, void* stream);
 
+#define TTS_LOSS_BCE 2  /* nn.BCEWithLogitsLoss, for the gradient only: the forward has its own entry point */
+
+/* The gradient of the five criteria with respect to input, for the loss.backward() of train.py:157: what
+ * autograd derives from layers/losses.py:30-32, 59-61 (input * mask, the summed loss, the division by
+ * mask.sum()) and from nn.L1Loss / nn.MSELoss / nn.BCEWithLogitsLoss, as one elementwise pass.  No handle:
+ * the call has no workspace and no host staging, so it shares nothing with a forward in flight.
+ *   input, target [dev]  fp32, B sentences of per_sentence = T * D elements, sentence b at b * pitch
+ *   n_valid       [dev]  int64 [B]: sentence b's valid elements min(lengths[b], T) * D, clamped on the device
+ *                        to [0, per_sentence]; NULL: per_sentence each (the plain criteria; BCE, with the
+ *                        logits cut into B equal runs of any length, e.g. one per row)
+ *   count         the forward's number of terms (the sum of n_valid), known to the host
+ *   grad_output   [dev]  one fp32, the upstream gradient autograd hands over, or NULL: 1.  Read on the device.
+ *   grad_input    [dev]  fp32 out, sentence b at b * grad_pitch
+ * A valid element (index < n_valid[b]) is formed in fp64 from the fp32 operands and rounded to fp32 once:
+ *   L1   grad_output * sign(x - y) / count, sign(0) = 0 as torch's l1_loss backward
+ *   MSE  grad_output * 2 (x - y) / count
+ *   BCE  grad_output * (sigmoid(x) - y) / count, the sigmoid as 1 / (1 + e^-x) for x >= 0 and
+ *        e^x / (1 + e^x) otherwise: nothing overflows
+ * Every element from n_valid[b] up to per_sentence is written +0.0; nothing between per_sentence and
+ * grad_pitch is written; input and target are NOT READ at or beyond n_valid[b].  With count = 0 every
+ * element of [B][per_sentence] is written NaN: the reference's 1 / mask.sum() is inf, and inf * 0 is NaN.
+ * INVALID before any launch: a null input, target or grad_input, an unknown kind, B or per_sentence <= 0, a
+ * pitch below per_sentence, a negative count.  One launch; does not wait for the stream and copies nothing
+ * to the host. */
+tts_status tts_loss_backward(int kind, const float* input, int64_t input_pitch, const float* target,
+                             int64_t target_pitch, const int64_t* n_valid, int B, int64_t per_sentence, int64_t count,
+                             const float* grad_output, float* grad_input, int64_t grad_pitch, void* stream);
+
 /* ---------------------------------------------------------------- training update
  * The tail of every training iteration (train.py:157-167) on parameters, gradients and Adam state that stay
  * in HBM: the custom weight decay, clip_grad_norm_ and torch.optim.Adam.step (weight_decay = 0, no amsgrad),

@@ -12,6 +12,7 @@ interface for the path:
 * ``datasets.collate_fn``, ``data.prepare_*`` <- ``datasets/TTSDataset.py``, ``utils/data.py``
 * ``losses.L1LossMasked / MSELossMasked``     <- ``layers/losses.py``
 * ``evaluate.evaluate_batch / evaluate``      <- ``train.py`` (``evaluate``)
+* ``train.train_batch``                       <- ``train.py`` (``train``, one iteration)
 * ``optim.Adam``, ``generic_utils.weight_decay / check_update / NoamLR`` <- ``train.py:157-167``, ``utils/generic_utils.py``
 
 The directory name is not a Python identifier; import with
@@ -23,4 +24,4 @@ import sys as _sys
 _sys.modules.setdefault("yvtts_amd", _sys.modules[__name__])
 
 __all__ = ["weights", "generic_utils", "tacotron2", "audio", "synthesis", "sharding", "data", "datasets", "losses",
-           "evaluate", "optim"]
+           "evaluate", "optim", "train"]

@@ -16,6 +16,7 @@ TTS_GL_FROM_MEL = 0
 TTS_GL_FROM_LINEAR = 1
 TTS_LOSS_L1 = 0
 TTS_LOSS_MSE = 1
+TTS_LOSS_BCE = 2  # tts_loss_backward only
 TTS_OPTIM_CHUNK = 8192  # elements per chunk of work of csrc/optim.hip (include/tts_hip.h)
 GL_PATHS = {0: "unfused", 1: "fused", 2: "persistent"}  # TTS_GL_PATH_* (include/tts_hip.h)
 DECODER_STEP_KERNELS = ("prenet2", "att_lstm", "query", "attention", "dec_lstm", "mel_fused")
@@ -41,7 +42,7 @@ EXPORTS = (
     "tts_tacotron_decode_teacher",
     "tts_tacotron_postnet", "tts_tacotron_last_timing", "tts_tacotron_last_path", "tts_tacotron_resident_phases",
     "tts_tacotron_profile",
-    "tts_loss_create", "tts_loss_destroy", "tts_loss_masked", "tts_loss_bce_logits",
+    "tts_loss_create", "tts_loss_destroy", "tts_loss_masked", "tts_loss_bce_logits", "tts_loss_backward",
     "tts_optim_create", "tts_optim_destroy", "tts_optim_set_tensors", "tts_optim_grad_norm", "tts_optim_clip",
     "tts_optim_decay", "tts_optim_adam", "tts_optim_step",
     "tts_last_error", "tts_version",
@@ -169,6 +170,8 @@ def _declare(lib):
     lib.tts_loss_masked.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64, I32P, ctypes.c_int,
                                     ctypes.c_int, ctypes.c_int, vp, vp, DP, I64P, DP, vp]
     lib.tts_loss_bce_logits.argtypes = [vp, vp, vp, ctypes.c_int64, vp, vp, DP, DP, vp]
+    lib.tts_loss_backward.argtypes = [ctypes.c_int, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, ctypes.c_int,
+                                      ctypes.c_int64, ctypes.c_int64, vp, vp, ctypes.c_int64, vp]
     OT, D = ctypes.POINTER(OptimTensor), ctypes.c_double
     lib.tts_optim_create.argtypes = [ctypes.POINTER(vp)]
     lib.tts_optim_destroy.argtypes = [vp]
@@ -187,7 +190,7 @@ def _declare(lib):
                           "_continue", "_basis", "_melspectrogram", "_path", "_sync", "_phases", "_teacher",
                           "_phase_state", "_pcm16", "_limits", "_analyze", "_to_mel", "_silence", "_endpoint",
                           "_segments", "_masked", "_logits", "_filter", "_resample", "_tensors", "_grad_norm",
-                          "_clip", "_decay", "_adam", "_step")):
+                          "_clip", "_decay", "_adam", "_step", "_backward")):
             fn.restype = ctypes.c_int
 
 

@@ -22,6 +22,8 @@
 // base is 16-byte aligned only by chance).  The loads are declared 4-byte aligned; gfx950 serves a
 // dword-aligned global_load_dwordx4, and an aligned base costs nothing extra.  Only a chunk's last,
 // partial quad is loaded by scalars.  No floating-point atomics, no in-launch hand-off between workgroups.
+//
+// The criteria's gradient for loss.backward() (train.py:157) is the third kernel, further down.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -36,7 +38,7 @@ constexpr int LOSS_WAVES = LOSS_THREADS / WAVE;
 constexpr int LOSS_QUADS = 8;                               // 16-byte loads per thread and operand
 constexpr int LOSS_CHUNK = LOSS_THREADS * 4 * LOSS_QUADS;   // elements per workgroup (2 x 32 KiB read)
 constexpr int FOLD_THREADS = 1024;                          // the fold: one workgroup, a wave per sentence in turn
-constexpr int KIND_BCE = 2;                                 // internal: after TTS_LOSS_L1, TTS_LOSS_MSE
+constexpr int KIND_BCE = TTS_LOSS_BCE;                      // the forward has its own entry point for it
 
 typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));
 
@@ -152,6 +154,111 @@ __global__ __launch_bounds__(FOLD_THREADS) void loss_fold_kernel(const FoldArgs 
     }
 }
 
+// ---------------------------------------------------------------- the gradient (train.py:157)
+// d loss / d input of the five criteria, elementwise: 8 bytes read and 4 written per valid element, 4
+// written per padding element, no reduction, no atomics, no hand-off.  The same cut as the forward
+// (LOSS_CHUNK elements by element index within a sentence, 16-byte accesses at element indices that are
+// multiples of four of the sentence, declared 4-byte aligned, a chunk's last partial quad by scalars), but
+// the grid covers every chunk of [B][T * D]: padding gets its zeros.  A chunk is entirely valid (all loads
+// in flight before the first value), entirely padding (stores only) or straddles n[b]; which, is
+// block-uniform.  x and y are never read at or beyond n[b].
+struct GradArgs {
+    const float* x;        // input / logits
+    const float* y;        // target
+    int64_t x_pitch, y_pitch;
+    const int64_t* n;      // [B] valid elements per sentence, or null: per each
+    int64_t per;           // T * D
+    int chunks_per;        // chunks per sentence
+    long long count;       // number of terms of the forward
+    const float* gout;     // device scalar, or null: 1
+    float* g;              // grad_input
+    int64_t g_pitch;
+};
+
+// the fp64 gradient of one element pair, rounded to fp32 once; scale = gout / count
+template <int KIND>
+__device__ __forceinline__ float loss_grad(float xf, float yf, double scale) {
+    const double x = (double)xf, y = (double)yf;
+    if (KIND == TTS_LOSS_L1) {
+        const double d = x - y;
+        return (float)(scale * (d > 0.0 ? 1.0 : d < 0.0 ? -1.0 : 0.0));  // sign(0) = 0, as torch's l1_loss backward
+    }
+    if (KIND == TTS_LOSS_MSE) return (float)(scale * (2.0 * (x - y)));
+    // BCEWithLogitsLoss: sigmoid(x) - y; exp's argument is <= 0, so no overflow
+    double sg;
+    if (x >= 0.0) sg = 1.0 / (1.0 + exp(-x));
+    else {
+        const double e = exp(x);
+        sg = e / (1.0 + e);
+    }
+    return (float)(scale * (sg - y));
+}
+
+template <int KIND>
+__global__ __launch_bounds__(LOSS_THREADS) void loss_grad_kernel(const GradArgs a) {
+    const int b = blockIdx.x / a.chunks_per;
+    const int64_t start = (int64_t)(blockIdx.x - b * a.chunks_per) * LOSS_CHUNK;
+    const int64_t room = a.per - start;  // >= 1: elements of [T * D] from this chunk's start on
+    const int cnt = room < LOSS_CHUNK ? (int)room : LOSS_CHUNK;
+    int64_t nb = a.n ? a.n[b] : a.per;
+    nb = nb < 0 ? 0 : nb > a.per ? a.per : nb;  // (a table out of range must not move an access out of [T * D])
+    const int64_t left = nb - start;
+    const int valid = left <= 0 ? 0 : left < cnt ? (int)left : cnt;
+    const float* x = a.x + (int64_t)b * a.x_pitch + start;
+    const float* y = a.y + (int64_t)b * a.y_pitch + start;
+    float* g = a.g + (int64_t)b * a.g_pitch + start;
+    const int tid = threadIdx.x;
+    // count 0: the reference's 1 / mask.sum() is inf and inf * 0 NaN on every element (all are padding then)
+    const float pad = a.count == 0 ? __builtin_nanf("") : 0.0f;
+    const float4u pad4 = {pad, pad, pad, pad};
+    if (valid == 0) {  // (block-uniform) padding only: nothing is loaded, not even grad_output
+        for (int j = 0; j < LOSS_QUADS; ++j) {
+            const int e = 4 * (tid + j * LOSS_THREADS);
+            if (e + 4 <= cnt) *reinterpret_cast<float4u*>(g + e) = pad4;
+            else
+                for (int c = 0; c < 4; ++c)
+                    if (e + c < cnt) g[e + c] = pad;
+        }
+        return;
+    }
+    const double scale = (a.gout ? (double)*a.gout : 1.0) / (double)a.count;
+    if (valid == LOSS_CHUNK) {  // (block-uniform) every load in flight before the first value
+        float4u vx[LOSS_QUADS], vy[LOSS_QUADS];
+#pragma unroll
+        for (int j = 0; j < LOSS_QUADS; ++j) {
+            const int e = 4 * (tid + j * LOSS_THREADS);
+            vx[j] = *reinterpret_cast<const float4u*>(x + e);
+            vy[j] = *reinterpret_cast<const float4u*>(y + e);
+        }
+#pragma unroll
+        for (int j = 0; j < LOSS_QUADS; ++j) {
+            float4u v;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) v[c] = loss_grad<KIND>(vx[j][c], vy[j][c], scale);
+            *reinterpret_cast<float4u*>(g + 4 * (tid + j * LOSS_THREADS)) = v;
+        }
+        return;
+    }
+    for (int j = 0; j < LOSS_QUADS; ++j) {  // the chunk that holds n[b], or the sentence's last one
+        const int e = 4 * (tid + j * LOSS_THREADS);
+        if (e + 4 <= valid) {
+            const float4u vx = *reinterpret_cast<const float4u*>(x + e);
+            const float4u vy = *reinterpret_cast<const float4u*>(y + e);
+            float4u v;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) v[c] = loss_grad<KIND>(vx[c], vy[c], scale);
+            *reinterpret_cast<float4u*>(g + e) = v;
+        } else if (e >= valid && e + 4 <= cnt) {
+            *reinterpret_cast<float4u*>(g + e) = pad4;
+        } else {
+            for (int c = 0; c < 4; ++c) {
+                if (e + c < valid) g[e + c] = loss_grad<KIND>(x[e + c], y[e + c], scale);
+                else if (e + c < cnt) g[e + c] = pad;
+            }
+        }
+    }
+}
+
 }  // namespace
 }  // namespace tts
 
@@ -257,6 +364,29 @@ tts_status tts_loss_bce_logits(tts_loss* h, const float* logits, const float* ta
     int64_t count;
     return loss_run(h, KIND_BCE, logits, 0, targets, 0, std::vector<int64_t>(1, n), sum_dev, loss_dev, sum_out, &count,
                     loss_out, static_cast<hipStream_t>(stream));
+}
+
+tts_status tts_loss_backward(int kind, const float* input, int64_t input_pitch, const float* target,
+                             int64_t target_pitch, const int64_t* n_valid, int B, int64_t per_sentence, int64_t count,
+                             const float* grad_output, float* grad_input, int64_t grad_pitch, void* stream) {
+    TTS_CHECK(input && target && grad_input, TTS_ERR_INVALID, "loss_backward: null argument");
+    TTS_CHECK(kind == TTS_LOSS_L1 || kind == TTS_LOSS_MSE || kind == TTS_LOSS_BCE, TTS_ERR_INVALID,
+              "loss_backward: kind must be L1, MSE or BCE");
+    TTS_CHECK(B >= 1 && per_sentence >= 1, TTS_ERR_INVALID, "loss_backward: B and per_sentence must be positive");
+    TTS_CHECK(input_pitch >= per_sentence && target_pitch >= per_sentence && grad_pitch >= per_sentence,
+              TTS_ERR_INVALID, "loss_backward: a batch pitch is below per_sentence");
+    TTS_CHECK(count >= 0, TTS_ERR_INVALID, "loss_backward: count is negative");
+    const int64_t chunks_per = (per_sentence + LOSS_CHUNK - 1) / LOSS_CHUNK;
+    TTS_CHECK(chunks_per * B <= INT32_MAX, TTS_ERR_INVALID, "loss_backward: more than 2^31 - 1 chunks of work");
+    GradArgs a{input, target, input_pitch, target_pitch, n_valid, per_sentence, (int)chunks_per, (long long)count,
+               grad_output, grad_input, grad_pitch};
+    const dim3 grid((unsigned)(chunks_per * B)), block(LOSS_THREADS);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (kind == TTS_LOSS_L1) hipLaunchKernelGGL(loss_grad_kernel<TTS_LOSS_L1>, grid, block, 0, s, a);
+    else if (kind == TTS_LOSS_MSE) hipLaunchKernelGGL(loss_grad_kernel<TTS_LOSS_MSE>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(loss_grad_kernel<TTS_LOSS_BCE>, grid, block, 0, s, a);
+    TTS_HIP(hipGetLastError());
+    return TTS_OK;
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-"""The reference's evaluation criteria on the device (train.py:462-465, layers/losses.py).
+"""The reference's criteria on the device (train.py:462-465, layers/losses.py), for evaluation and training.
 
 ``L1LossMasked`` / ``MSELossMasked`` keep the reference's ``(input, target, length)`` call, ``L1Loss`` /
 ``MSELoss`` / ``BCEWithLogitsLoss`` torch.nn's ``(input, target)``; each returns a 0-dim CUDA float32 tensor.
@@ -11,14 +11,23 @@ both operands, fp64 arithmetic, a fixed summation order.  After a call
   ``last_per_sentence``  CUDA float64 [B]: each sentence's sum (BCEWithLogitsLoss: [1], the whole sum)
 
 Rows at and beyond a sentence's length are not read, so a NaN there does not reach the result (the
-reference's ``NaN * 0`` does).  Evaluation only: nothing here has a gradient.  Without a GPU the classes
-raise the package's "no GPU" RuntimeError; there is no CPU fallback.
+reference's ``NaN * 0`` does).
+
+With grad mode on and an ``input`` that requires grad, the call joins autograd: the forward is the same (the
+same kernels, bitwise the same values), and ``loss.backward()`` (train.py:157) runs ``tts_loss_backward``, one
+elementwise launch on the current stream that waits for nothing: every valid element's gradient formed in
+fp64 and rounded once, ``+0.0`` on the padding rows, NaN everywhere when no sentence has a valid row (the
+reference's ``inf * 0``).  Such an input must be a CUDA float32 tensor (a silent ``.to()`` would cut the
+graph); the target and the lengths get no gradient (the reference sets ``target.requires_grad = False``), and
+there is no double backward.  Without a GPU the classes raise the package's "no GPU" RuntimeError; there is
+no CPU fallback.
 """
 from __future__ import annotations
 
 import ctypes
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _native
 
@@ -26,6 +35,43 @@ from . import _native
 def _operand(t):
     t = torch.as_tensor(t)
     return t.detach().to("cuda", torch.float32)
+
+
+def _differentiable(input):
+    """True when the call has to join autograd; such an input is used as it is, so it must be CUDA float32."""
+    if not (torch.is_grad_enabled() and isinstance(input, torch.Tensor) and input.requires_grad):
+        return False
+    if not input.is_cuda or input.dtype != torch.float32:
+        raise ValueError(f"an input that requires grad must be a CUDA float32 tensor, got {input.dtype} on "
+                         f"{input.device}: a conversion here would cut the graph")
+    return True
+
+
+class _Criterion(torch.autograd.Function):
+    """``crit._forward`` as it is, with ``tts_loss_backward`` behind it.  ``_forward`` returns the loss and what
+    the gradient needs: the fp32 CUDA operands it ran on, their pitches, the device table of valid elements per
+    sentence (None: all), B, T * D and the number of terms."""
+
+    @staticmethod
+    def forward(ctx, input, crit, target, length):
+        loss, (x, xp, y, yp, n_valid, B, per, count) = crit._forward(input, target, length, grad=True)
+        ctx.save_for_backward(x, y, *(() if n_valid is None else (n_valid,)))
+        ctx.call = (crit.KIND, xp, yp, B, per, count, input.shape)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        x, y, *n_valid = ctx.saved_tensors
+        kind, xp, yp, B, per, count, shape = ctx.call
+        gout = grad_output.to(x.device, torch.float32).contiguous()  # (the 0-dim tensor autograd hands over, as it is)
+        grad = torch.empty(B, per, dtype=torch.float32, device=x.device)
+        _native.check(_native.lib().tts_loss_backward(
+            kind, ctypes.c_void_p(x.data_ptr()), xp, ctypes.c_void_p(y.data_ptr()), yp,
+            ctypes.c_void_p(n_valid[0].data_ptr()) if n_valid else None, B, per, count,
+            ctypes.c_void_p(gout.data_ptr()), ctypes.c_void_p(grad.data_ptr()), per, _native.stream_handle()),
+            "tts_loss_backward")
+        return grad.view(shape), None, None, None
 
 
 class _Loss:
@@ -54,6 +100,11 @@ class _Loss:
     def forward(self, *args):
         return self(*args)
 
+    def _run(self, input, target, length=None):
+        if _differentiable(input):
+            return _Criterion.apply(input, self, target, length)
+        return self._forward(input, target, length)[0]
+
 
 def _rows(t):
     """t as [B][T][D] with contiguous rows: (tensor kept alive, B, T, D, batch pitch in elements)."""
@@ -68,17 +119,19 @@ def _rows(t):
 class _Elementwise(_Loss):
     KIND = None
 
-    def _run(self, input, target, length):
+    def _forward(self, input, target, length, grad=False):
         lib, h = self._handle()
         x, B, T, D, xp = _rows(_operand(input))
         y, By, Ty, Dy, yp = _rows(_operand(target))
         if (B, T, D) != (By, Ty, Dy):
             raise ValueError(f"input {tuple(x.shape)} and target {tuple(y.shape)} differ in shape")
-        lens = None
+        lens = n_valid = None
         if length is not None:
             lens = [int(v) for v in torch.as_tensor(length).reshape(-1)]
             if len(lens) != B:
                 raise ValueError(f"{len(lens)} lengths for a batch of {B}")
+            if grad:  # the gradient reads the table on the device, after this call has returned
+                n_valid = torch.tensor([min(max(v, 0), T) * D for v in lens], dtype=torch.int64).to(x.device)
             lens = _native.i32_array(lens)
         per = torch.empty(B, dtype=torch.float64, device=x.device)
         loss = torch.empty((), dtype=torch.float32, device=x.device)
@@ -90,7 +143,7 @@ class _Elementwise(_Loss):
                                           _native.stream_handle()), "tts_loss_masked")
         self.last_value, self.last_count, self.last_sum = value.value, count.value, total.value
         self.last_per_sentence = per
-        return loss
+        return loss, (x, xp, y, yp, n_valid, B, T * D, count.value)
 
 
 class _Masked(_Elementwise):
@@ -121,7 +174,12 @@ class MSELoss(_Unmasked):  # nn.MSELoss(), train.py:464
 
 
 class BCEWithLogitsLoss(_Loss):  # nn.BCEWithLogitsLoss(), train.py:465
+    KIND = _native.TTS_LOSS_BCE
+
     def __call__(self, input, target):
+        return self._run(input, target)
+
+    def _forward(self, input, target, length=None, grad=False):
         lib, h = self._handle()
         x, y = _operand(input).contiguous(), _operand(target).contiguous()
         if x.shape != y.shape:
@@ -135,4 +193,6 @@ class BCEWithLogitsLoss(_Loss):  # nn.BCEWithLogitsLoss(), train.py:465
                                               ctypes.byref(value), _native.stream_handle()), "tts_loss_bce_logits")
         self.last_value, self.last_count, self.last_sum = value.value, x.numel(), total.value
         self.last_per_sentence = per
-        return loss
+        # the gradient's grid is per leading row ([B, steps] stop logits: a workgroup per sentence, not n / 8192 in all)
+        rows = x.shape[0] if x.dim() > 1 else 1
+        return loss, (x, x.numel() // rows, y, x.numel() // rows, None, rows, x.numel() // rows, x.numel())
