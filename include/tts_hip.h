@@ -84,6 +84,19 @@ tts_status tts_encoder_add_speakers(tts_encoder* e, float* enc, const int32_t* l
 /* The last run's BiLSTM path: 1 the resident batch-1 launch, 2 the batched resident launch
  * (2 <= B <= 64), 0 the per-step launches (see tts_encoder_run_state). */
 tts_status tts_encoder_last_path(tts_encoder* e, int* resident);
+/* Resident batch-1 launches of this handle that were rerun with the per-step launches: because the
+ * runtime placed too few workgroups on an XCD (placement_failures), or because a hand-off wait
+ * timed out beside another stream's work (timeouts). */
+tts_status tts_encoder_counters(tts_encoder* e, int* placement_failures, int* timeouts);
+/* The rule a handle applies to the status word (salt << 8 | code) of its resident batch-1 launch
+ * `salt`; host arithmetic only, no device.  *outcome: TTS_ENC_RUN_OK (and *fails_in_row = 0),
+ * TTS_ENC_RUN_PLACEMENT (++*fails_in_row; *resident = 0 once that reaches 3 sentences in a row, the
+ * decoder's rule) or TTS_ENC_RUN_TIMEOUT (both unchanged).  Either failure reruns that sentence
+ * per-step. */
+#define TTS_ENC_RUN_OK 0
+#define TTS_ENC_RUN_PLACEMENT 1
+#define TTS_ENC_RUN_TIMEOUT 2
+tts_status tts_encoder_status_rule(int status_word, unsigned salt, int* fails_in_row, int* resident, int* outcome);
 
 /* Decoder flags: the arguments of layers/tacotron2.py:98-100 (Decoder.__init__) that change
  * inference numerics, as mapped from the JSON config by utils/generic_utils.py:275-288. */
@@ -408,6 +421,11 @@ tts_status tts_synth_run_speakers(tts_synth* s, const int32_t* ids, const int32_
  * hand-off timeout) is otherwise collected by the next run.  This waits for the last run and
  * returns that status.  A failed run's waveform is NaN, never a plausible-looking signal. */
 tts_status tts_synth_sync(tts_synth* s);
+/* *last_front: the last run's encoder stage ran on the handle's own stream, beside the work the
+ * caller's stream still had in flight (batch 1 only; TTS_SYNTH_FRONT=0 turns it off);
+ * *in_flight (or NULL: not asked): a stream this handle's runs work on still has work queued
+ * (stream queries, no wait). */
+tts_status tts_synth_state(tts_synth* s, int* last_front, int* in_flight);
 
 /* ---------------------------------------------------------------- Tacotron / TacotronGST
  * SURVEY config 5 (config_tacotron_gst.json) and config_tacotron.json: the r-frames-per-step

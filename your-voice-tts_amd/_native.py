@@ -28,6 +28,7 @@ TACOTRON_STEP_KERNELS = ("prenet2", "att_gru", "query", "attention", "proj", "de
 EXPORTS = (
     "tts_encoder_create", "tts_encoder_destroy", "tts_encoder_run", "tts_encoder_run_state", "tts_encoder_last_path",
     "tts_encoder_add_speakers", "tts_synth_run_speakers",
+    "tts_encoder_counters", "tts_encoder_status_rule", "tts_synth_state",
     "tts_decoder_create", "tts_decoder_destroy", "tts_decoder_run", "tts_decoder_run_continue", "tts_decoder_run_teacher",
     "tts_decoder_last_timing", "tts_decoder_last_path", "tts_decoder_resident_limits", "tts_decoder_resident_phases", "tts_decoder_resident_trace",
     "tts_decoder_profile",
@@ -108,6 +109,10 @@ def _declare(lib):
     lib.tts_encoder_last_path.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
     lib.tts_gl_last_path.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
     lib.tts_synth_sync.argtypes = [vp]
+    IP = ctypes.POINTER(ctypes.c_int)
+    lib.tts_encoder_counters.argtypes = [vp, IP, IP]
+    lib.tts_encoder_status_rule.argtypes = [ctypes.c_int, ctypes.c_uint, IP, IP, IP]
+    lib.tts_synth_state.argtypes = [vp, IP, IP]
     lib.tts_decoder_resident_phases.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.c_int]
     lib.tts_decoder_resident_trace.argtypes = [vp, ctypes.POINTER(ctypes.c_longlong), ctypes.c_int64]
     lib.tts_postnet_create.argtypes = [ctypes.POINTER(TensorView), ctypes.c_int, ctypes.c_int, vp, ctypes.POINTER(vp)]
@@ -190,7 +195,7 @@ def _declare(lib):
                           "_continue", "_basis", "_melspectrogram", "_path", "_sync", "_phases", "_teacher",
                           "_phase_state", "_pcm16", "_limits", "_analyze", "_to_mel", "_silence", "_endpoint",
                           "_segments", "_masked", "_logits", "_filter", "_resample", "_tensors", "_grad_norm",
-                          "_clip", "_decay", "_adam", "_step", "_backward")):
+                          "_clip", "_decay", "_adam", "_step", "_backward", "_counters", "_rule")):
             fn.restype = ctypes.c_int
 
 

@@ -57,6 +57,8 @@ struct tts_encoder {
     bool lens_staged = false;   // pipeline: the caller wrote T on the stream already (stage_ids)
     bool skip_resident_once = false;  // a pipelined resident run timed out: its rerun goes per-step
     int res_timeouts = 0;             // resident runs that timed out a hand-off and re-ran per-step
+    int res_place_fails = 0;          // batch-1 resident placement failures in a row (RES_PLACEMENT_RETRIES)
+    int res_placements = 0;           // ... and over the life of the handle (tts_encoder_counters)
     std::map<int, hipGraphExec_t> rgraphs;  // by Lmax (B = 1)
     // batched resident BiLSTM (encoder_resident.h, 2 <= B <= 64, no caller state)
     float* whh_raw = nullptr;                // [2][1024][256] W_hh, reference layout
@@ -188,9 +190,46 @@ tts_status enqueue_encoder_resident(tts_encoder* e, int Lmax, bool zero_state, h
     return TTS_OK;
 }
 
+// the batch-1 resident launch `salt` from its status word in host_status[0] (left decoded there):
+// the handle's counters and its resident flag by tts_encoder_status_rule
+int resident_outcome(tts_encoder* e, unsigned salt) {
+    int outcome = TTS_ENC_RUN_OK, resident = e->resident ? 1 : 0;
+    (void)tts_encoder_status_rule(e->host_status[0], salt, &e->res_place_fails, &resident, &outcome);
+    e->host_status[0] = res_status_code(e->host_status[0], salt);
+    e->resident = resident != 0;
+    if (outcome == TTS_ENC_RUN_PLACEMENT) ++e->res_placements;
+    if (outcome == TTS_ENC_RUN_TIMEOUT) ++e->res_timeouts;
+    return outcome;
+}
+
 }  // namespace
 
 extern "C" {
+
+tts_status tts_encoder_status_rule(int status_word, unsigned salt, int* fails_in_row, int* resident, int* outcome) {
+    TTS_CHECK(fails_in_row && resident && outcome, TTS_ERR_INVALID, "null argument");
+    const int code = res_status_code(status_word, salt);
+    if (code == ENC_RES_STATUS_PLACEMENT) {
+        // one uneven dispatch (beside another stream's grid) is not a device that cannot place the
+        // grid: the handle gives the resident form up after RES_PLACEMENT_RETRIES sentences in a row,
+        // as the decoder does (decoder_api.hip: run_resident_one)
+        if (++*fails_in_row >= RES_PLACEMENT_RETRIES) *resident = 0;
+        *outcome = TTS_ENC_RUN_PLACEMENT;
+    } else if (code != 0) {
+        *outcome = TTS_ENC_RUN_TIMEOUT;  // the handle stays resident; the row of placement failures goes on
+    } else {
+        *fails_in_row = 0;
+        *outcome = TTS_ENC_RUN_OK;
+    }
+    return TTS_OK;
+}
+
+tts_status tts_encoder_counters(tts_encoder* e, int* placement_failures, int* timeouts) {
+    TTS_CHECK(e && placement_failures && timeouts, TTS_ERR_INVALID, "null argument");
+    *placement_failures = e->res_placements;
+    *timeouts = e->res_timeouts;
+    return TTS_OK;
+}
 
 void tts_encoder_destroy(tts_encoder* e) {
     if (!e) return;
@@ -416,19 +455,12 @@ tts_status tts_encoder_run_state(tts_encoder* e, const int32_t* ids, const int32
                 goto done;
             }
             TTS_HIP(hipStreamSynchronize(s));
-            e->host_status[0] = res_status_code(e->host_status[0], e->rsalt);
-            if (e->host_status[0] == ENC_RES_STATUS_PLACEMENT) {
-                e->resident = false;  // rerun below with the per-step launches (same state, untouched)
-                if (tts_status st = init_state()) return st;
-            } else if (e->host_status[0] != 0) {
-                // a hand-off wait timed out (a workgroup could not be placed beside another stream's
-                // work): the grid drained; rerun this call with the per-step launches from the
-                // initial state (state_in is still the caller's), the handle stays resident
-                ++e->res_timeouts;
-                if (tts_status st = init_state()) return st;
-            } else {
-                goto done;
-            }
+            // placement failure: rerun below with the per-step launches (same state, untouched);
+            // a hand-off wait timed out (a workgroup could not be placed beside another stream's
+            // work): the grid drained; rerun this call with the per-step launches from the
+            // initial state (state_in is still the caller's), the handle stays resident
+            if (resident_outcome(e, e->rsalt) == TTS_ENC_RUN_OK) goto done;
+            if (tts_status st = init_state()) return st;
         }
     }
     static const bool batch_off = env_is("TTS_ENC_BATCH_RESIDENT", '0');  // A/B knob
@@ -552,10 +584,18 @@ tts_status encoder_pending_status(tts_encoder* e, int* placement_failed) {
     *placement_failed = 0;
     if (!e->status_pending) return TTS_OK;
     e->status_pending = false;  // the caller synchronised the stream the status copy ran on
+    if (!e->pending_batch) {
+        // batch 1: a placement failure or a timed-out hand-off wait reruns once per-step; the handle
+        // keeps the resident form until RES_PLACEMENT_RETRIES placement failures in a row
+        if (resident_outcome(e, e->rsalt_pending) != TTS_ENC_RUN_OK) {
+            e->skip_resident_once = true;
+            *placement_failed = 1;
+        }
+        return TTS_OK;
+    }
     e->host_status[0] = res_status_code(e->host_status[0], e->rsalt_pending);
     if (e->host_status[0] == ENC_RES_STATUS_PLACEMENT) {
-        if (e->pending_batch) e->bgran = nullptr;  // the batched form cannot be placed on this device
-        else e->resident = false;
+        e->bgran = nullptr;  // the batched form cannot be placed on this device
         *placement_failed = 1;
         return TTS_OK;
     }

@@ -9,6 +9,14 @@
 // second stream of this handle, so call k+1's encoder + decoder (which read only host inputs and
 // this handle's buffers) need not wait for call k's Griffin-Lim; the stage buffers Griffin-Lim
 // reads (mel_post, its compacted copy) alternate per call.
+//
+// Batch 1 (the latency path) works on the caller's stream.  When that stream still has work in
+// flight at entry (a caller pipelining sentences with sync = false: call k's postnet and
+// Griffin-Lim), call k+1's encoder stage -- ids staging, the three convolutions, the input
+// projection, the resident BiLSTM, the speaker embedding -- runs on this handle's own stream beside
+// it, and the caller's stream waits for one event ahead of the decoder (synth_stages; hazards:
+// DESIGN.md section 10, round 13).  A lone sentence (idle caller stream) runs as before, no event.
+// TTS_SYNTH_FRONT=0 (read per call) keeps the encoder stage on the caller's stream.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -38,6 +46,9 @@ struct tts_synth {
     // waits for Griffin-Lim.
     hipStream_t stream = nullptr, gl_stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_post = nullptr, ev_out = nullptr;
+    // batch 1 on the caller's stream: the end of an encoder stage that ran on `stream` (synth_stages)
+    hipEvent_t ev_front = nullptr;
+    bool last_front = false;  // the last run's encoder stage ran there (tts_synth_state)
     // pinned host staging of ids / lens / frames, alternated per call: call k reuses call k-2's
     // buffer, whose copies completed before call k-1's decoder synchronisation and Griffin-Lim
     // collection
@@ -76,7 +87,7 @@ struct PipelineScope {
 // the stages of one tts_synth_run after the host staging (defined below)
 tts_status synth_stages(tts_synth* s, int32_t* h_ids, int32_t* h_lens, const int32_t* spk, int32_t* h_frames, int B,
                         int Lmax, int max_steps, int gl_iters, uint64_t seed, double* wav, int64_t wav_cap,
-                        int32_t* frames, void* stream);
+                        int32_t* frames, void* stream, bool cs_busy);
 tts_status synth_run(tts_synth* s, const int32_t* ids, const int32_t* lens, const int32_t* spk, int B, int Lmax,
                      int max_steps, int gl_iters, uint64_t seed, double* wav, int64_t wav_cap, int32_t* frames,
                      void* stream);
@@ -109,6 +120,7 @@ tts_status tts_synth_create(tts_encoder* e, tts_decoder* d, tts_postnet* p, tts_
         hipEventCreateWithFlags(&s->ev_in, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&s->ev_post, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&s->ev_out, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&s->ev_front, hipEventDisableTiming) != hipSuccess ||
         hipMalloc(&s->fspec, 4 * sizeof(int)) != hipSuccess) {
         tts_synth_destroy(s);
         tts::set_error("tts_synth_create: stream / event creation failed");
@@ -131,7 +143,7 @@ void tts_synth_destroy(tts_synth* s) {
         if (q) (void)hipFree(q);
     for (int32_t* q : s->pin)
         if (q) (void)hipHostFree(q);
-    for (hipEvent_t ev : {s->ev_in, s->ev_post, s->ev_out})
+    for (hipEvent_t ev : {s->ev_in, s->ev_post, s->ev_out, s->ev_front})
         if (ev) (void)hipEventDestroy(ev);
     for (hipStream_t q : {s->stream, s->gl_stream})
         if (q) (void)hipStreamDestroy(q);
@@ -162,6 +174,10 @@ tts_status synth_run(tts_synth* s, const int32_t* ids, const int32_t* lens, cons
     const size_t T = (size_t)cap * s->r;
     tts_status st;
     hipStream_t cs = static_cast<hipStream_t>(stream);
+    // whether the caller's stream has work in flight as this call begins (synth_stages' front stream;
+    // asked before a regrow below drains it)
+    const bool cs_busy = hipStreamQuery(cs) == hipErrorNotReady;
+    (void)hipGetLastError();  // "not ready" is an answer, not an error to keep
     // buffers are only (re)allocated with nothing of this pipeline in flight (a batch-1 run works on
     // the caller's stream: synth_stages)
     const bool regrow = (size_t)B * Lmax > s->ids_n || (size_t)B * Lmax * 512 > s->enc_n ||
@@ -204,7 +220,8 @@ tts_status synth_run(tts_synth* s, const int32_t* ids, const int32_t* lens, cons
     std::copy(lens, lens + B, h_lens);
     // a call that fails after staging may still have copies from pin[par] in flight: drain them
     // before returning, so the next call can restage the same buffer
-    st = synth_stages(s, h_ids, h_lens, spk, h_frames, B, Lmax, max_steps, gl_iters, seed, wav, wav_cap, frames, stream);
+    st = synth_stages(s, h_ids, h_lens, spk, h_frames, B, Lmax, max_steps, gl_iters, seed, wav, wav_cap, frames, stream,
+                      cs_busy);
     if (st) {
         (void)hipStreamSynchronize(s->stream);
         (void)hipStreamSynchronize(s->gl_stream);
@@ -226,12 +243,27 @@ tts_status tts_synth_sync(tts_synth* s) {
     return tts::gl_collect(s->g);
 }
 
+tts_status tts_synth_state(tts_synth* s, int* last_front, int* in_flight) {
+    TTS_CHECK(s && last_front, TTS_ERR_INVALID, "null argument");
+    *last_front = s->last_front ? 1 : 0;
+    if (!in_flight) return TTS_OK;
+    *in_flight = 0;
+    // (last_cs: null is also the legacy default stream, which a batch-1 run may have worked on)
+    for (hipStream_t q : {s->stream, s->gl_stream, s->last_cs}) {
+        const hipError_t e = hipStreamQuery(q);
+        (void)hipGetLastError();  // "not ready" is an answer, not an error to keep
+        if (e == hipErrorNotReady) *in_flight = 1;
+        else TTS_HIP(e);
+    }
+    return TTS_OK;
+}
+
 }  // extern "C"
 
 namespace {
 tts_status synth_stages(tts_synth* s, int32_t* h_ids, int32_t* h_lens, const int32_t* spk, int32_t* h_frames, int B,
                         int Lmax, int max_steps, int gl_iters, uint64_t seed, double* wav, int64_t wav_cap,
-                        int32_t* frames, void* stream) {
+                        int32_t* frames, void* stream, bool cs_busy) {
     hipStream_t cs = static_cast<hipStream_t>(stream);
     // a batch-1 run (the latency path) works on the caller's stream itself: every stage in stream
     // order behind the caller's earlier work, and no cross-stream event between this call's stages
@@ -241,6 +273,17 @@ tts_status synth_stages(tts_synth* s, int32_t* h_ids, int32_t* h_lens, const int
     static const bool own_stream = tts::env_is("TTS_SYNTH_OWN_STREAM", '1');
     hipStream_t ss = B == 1 && !own_stream ? cs : s->stream;
     s->last_cs = ss == cs ? cs : nullptr;
+    // ... except the encoder stage of a call that found the caller's stream busy at its entry (the
+    // previous call's postnet and Griffin-Lim: the persistent loop holds one wave per SIMD for
+    // ~0.35 ms): it reads host ids and writes the encoder handle's buffers only, which nothing
+    // after the previous call's decoder reads, and that decoder had finished when the previous call
+    // returned.  It goes to this handle's own stream (in order behind any earlier front stage), and
+    // cs waits for its end ahead of the decoder: one event hand-off (~6 us) against the stage's
+    // ~0.13 ms.  An idle caller stream (a lone sentence) gains nothing from it and pays no event.
+    // TTS_SYNTH_FRONT=0 turns it off (measurement; read per call, so one process can run both).
+    const bool front = ss == cs && cs_busy && !tts::env_is("TTS_SYNTH_FRONT", '0');
+    s->last_front = front;
+    hipStream_t es = front ? s->stream : ss;  // the encoder stage's stream
     const int cap = max_steps + 21;
     const size_t T = (size_t)cap * s->r;
     tts_status st;
@@ -267,10 +310,10 @@ tts_status synth_stages(tts_synth* s, int32_t* h_ids, int32_t* h_lens, const int
         sa.n = Lmax;
         sa.len = h_lens[0];
         std::copy(h_ids, h_ids + Lmax, sa.v);
-        TTS_HIP(tts::stage_ids(sa, ss));
+        TTS_HIP(tts::stage_ids(sa, es));
         tts::encoder_set_lens_staged(s->e, true);
     } else {
-        TTS_HIP(hipMemcpyAsync(ids_dev, h_ids, sizeof(int32_t) * (size_t)B * Lmax, hipMemcpyHostToDevice, ss));
+        TTS_HIP(hipMemcpyAsync(ids_dev, h_ids, sizeof(int32_t) * (size_t)B * Lmax, hipMemcpyHostToDevice, es));
         tts::encoder_set_lens_staged(s->e, false);
     }
     s->steps.assign(B, 0);
@@ -347,9 +390,14 @@ tts_status synth_stages(tts_synth* s, int32_t* h_ids, int32_t* h_lens, const int
     static const bool no_hook = tts::env_is("TTS_NO_HOOK", '1');
     tts::decoder_set_post_hook(s->d, B == 1 && !no_hook ? +hook_fn : nullptr, &hook);
     for (int attempt = 0;; ++attempt) {
-        if ((st = tts_encoder_run(s->e, ids_dev, h_lens, B, Lmax, enc, ss))) return st;
+        if (attempt == 1) es = ss;  // a rerun: cs is behind the front stage's event already
+        if ((st = tts_encoder_run(s->e, ids_dev, h_lens, B, Lmax, enc, es))) return st;
         // Tacotron2._add_speaker_embedding (models/tacotron2.py:65, 91-100)
-        if (spk && (st = tts::encoder_add_speakers(s->e, enc, h_lens, spk, B, Lmax, ss))) return st;
+        if (spk && (st = tts::encoder_add_speakers(s->e, enc, h_lens, spk, B, Lmax, es))) return st;
+        if (es != ss) {
+            TTS_HIP(hipEventRecord(s->ev_front, es));
+            TTS_HIP(hipStreamWaitEvent(ss, s->ev_front, 0));
+        }
         // synchronises ss: the encoder's placement status is then readable
         st = tts_decoder_run(s->d, enc, h_lens, B, Lmax, max_steps, cap, s->mel, s->stop, nullptr, s->steps.data(), ss);
         if (!st) st = hook.st;

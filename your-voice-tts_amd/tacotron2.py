@@ -415,6 +415,10 @@ class Tacotron2:
         if sync:
             _native.check(lib.tts_synth_sync(hs), "tts_synth_sync")
         self.last_timing = self._path_timing(lib, hdec)
+        front = ctypes.c_int()
+        _native.check(lib.tts_synth_state(hs, ctypes.byref(front), None), "tts_synth_state")
+        # the call's encoder stage ran on the handle's own stream, beside the previous call's tail
+        self.last_timing["encoder_front"] = bool(front.value)
         self.last_lengths = frames
         n = ap.hop_length * (max(frames) - 1)
         return wav_buf.view(-1)[:B * n].view(B, n), frames
@@ -447,8 +451,11 @@ class Tacotron2:
         lib.tts_decoder_last_timing(hdec, ctypes.byref(ms), ctypes.byref(ns))
         lib.tts_decoder_last_path(hdec, ctypes.byref(res))
         lib.tts_encoder_last_path(self._native[3], ctypes.byref(enc))
+        npl, ntm = ctypes.c_int(), ctypes.c_int()
+        lib.tts_encoder_counters(self._native[3], ctypes.byref(npl), ctypes.byref(ntm))
         return dict(decoder_loop_ms=ms.value, decoder_steps_run=ns.value, resident=bool(res.value),
-                    resident_kind=int(res.value), encoder_resident=bool(enc.value), encoder_path=int(enc.value))
+                    resident_kind=int(res.value), encoder_resident=bool(enc.value), encoder_path=int(enc.value),
+                    encoder_placement_failures=npl.value, encoder_timeouts=ntm.value)
 
     RESIDENT_PHASES = ("att_early_wait_pre1", "prenet2_row", "wait_prenet2", "att_lstm_prenet", "att_cell_gather",
                        "query_dec_early", "wait_query", "energies_max", "weights_ctx_publish", "dec_lstm_hatt",
