@@ -460,10 +460,22 @@ void tts_tacotron_destroy(tts_tacotron* t);
  *   speaker_ids [host] int32 [B] or NULL
  *   style_mel   [dev]  fp32 [B][style_frames][80] or NULL (GST models only)
  *   out         [dev]  fp32 [B][Lmax][256], every sentence encoded at its own length, rows past
- *                      lens[b] zero. */
+ *                      lens[b] zero (+0.0, every bit clear).
+ * Padding contract of ids: entries ids[b][t], t >= lens[b], are never read as table rows and may
+ * hold anything (negative values and values past the table included); Lmax may exceed the longest
+ * lens[b].  Entries t < lens[b] must be rows of embedding.weight.  A speaker id outside
+ * [0, num_speakers), style_mel on a model without GST, style_frames < 1 with style_mel, a lens[b]
+ * outside [1, Lmax] or B / Lmax above the handle's capacity return TTS_ERR_INVALID and leave out
+ * untouched.  speaker_ids are ignored by a model with num_speakers <= 1. */
 tts_status tts_tacotron_encode(tts_tacotron* t, const int32_t* ids, const int32_t* lens, int B, int Lmax,
                                const int32_t* speaker_ids, const float* style_mel, int style_frames, float* out,
                                void* stream);
+/* Which convolution kernel served each launch of the last tts_tacotron_encode (no reference
+ * counterpart; the values of tts_postnet_last_path): kinds[0..9] = prenet layers 1, 2, the conv
+ * bank, projections 1, 2, highways 1-4, the BiGRU input projection; kinds[10] = the GST GRU input
+ * projection, -1 if the call had no style_mel.  n >= 11; -1 before the first call.  3 (16-frame
+ * tiles) up to sum lens[b] = 4096 frames, 8 (64-frame tiles) above. */
+tts_status tts_tacotron_encode_last_path(tts_tacotron* t, int* kinds, int n);
 
 /* Replaces Decoder.inference (layers/tacotron.py:439-470) for a padded batch with per-sentence
  * batch-1 semantics (the reference's stop rule is batch-1, :464-469):

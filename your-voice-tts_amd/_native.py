@@ -39,7 +39,8 @@ EXPORTS = (
     "tts_gl_trim_silence", "tts_gl_find_endpoint", "tts_gl_take_segments",
     "tts_gl_set_resample_filter", "tts_gl_resample",
     "tts_synth_create", "tts_synth_destroy", "tts_synth_run", "tts_synth_sync",
-    "tts_tacotron_create", "tts_tacotron_destroy", "tts_tacotron_encode", "tts_tacotron_decode",
+    "tts_tacotron_create", "tts_tacotron_destroy", "tts_tacotron_encode", "tts_tacotron_encode_last_path",
+    "tts_tacotron_decode",
     "tts_tacotron_decode_teacher",
     "tts_tacotron_postnet", "tts_tacotron_last_timing", "tts_tacotron_last_path", "tts_tacotron_resident_phases",
     "tts_tacotron_profile",
@@ -159,6 +160,7 @@ def _declare(lib):
     lib.tts_tacotron_destroy.argtypes = [vp]
     lib.tts_tacotron_destroy.restype = None
     lib.tts_tacotron_encode.argtypes = [vp, vp, I32P, ctypes.c_int, ctypes.c_int, I32P, vp, ctypes.c_int, vp, vp]
+    lib.tts_tacotron_encode_last_path.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
     lib.tts_tacotron_decode.argtypes = [vp, vp, I32P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp,
                                         vp, I32P, vp]
     lib.tts_tacotron_decode_teacher.argtypes = [vp, vp, I32P, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int64,

@@ -122,6 +122,9 @@ struct tts_tacotron {
     long long res_ticks = 0;
     unsigned res_salt = 0;
     int res_timeouts = 0, last_resident = 0;
+    // ConvKind of the last tts_tacotron_encode's launches (tts_tacotron_encode_last_path): prenet x2,
+    // bank, projections x2, highways x4, GRU input, then the GST projection (-1: no style)
+    int enc_kind[11] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
     TResArgs last_ra{};
     // last decode (profiling)
     float last_ms = 0.f;
@@ -269,9 +272,13 @@ tts_status make_cbhg(tts_tacotron* t, Cbhg& c, const WeightMap& wm, const std::s
     return TTS_OK;
 }
 
-// CBHG.forward over a padded batch: x [B][Tmax][cin] -> out [B][Tmax][256] (rows past T_b untouched)
+// CBHG.forward over a padded batch: x [B][Tmax][cin] -> out [B][Tmax][256] (rows past T_b untouched).
+// `kinds` (optional, 8 entries; no pre_highway): the ConvKind of the bank, the projections, the
+// highways and the GRU input projection.
 tts_status run_cbhg(tts_tacotron* t, const Cbhg& c, const float* x, int B, int Tmax, int frames, float* out,
-                    const float* add1, const float* add2, hipStream_t s) {
+                    const float* add1, const float* add2, hipStream_t s, int* kinds = nullptr) {
+    int unused[8];
+    if (!kinds) kinds = unused;
     const size_t BT = (size_t)B * Tmax;
     tts_status st;
     if ((st = grow(t, t->bank, BT * c.K * 128)) || (st = grow(t, t->p0, BT * c.p0)) || (st = grow(t, t->y, BT * c.p1)) ||
@@ -290,7 +297,7 @@ tts_status run_cbhg(tts_tacotron* t, const Cbhg& c, const float* x, int B, int T
     a.Cout = c.K * 128;
     a.co_pad = c.K * 128;
     a.act = CONV_RELU;
-    TTS_HIP(conv_launch(a, c.K, B, frames, s));
+    TTS_HIP(conv_launch(a, c.K, B, frames, s, &kinds[0]));
     // max_pool1d fused into the first projection (+ BN + ReLU)
     a = ConvArgs{};
     a.T = t->T;
@@ -305,7 +312,7 @@ tts_status run_cbhg(tts_tacotron* t, const Cbhg& c, const float* x, int B, int T
     a.Cout = c.p0;
     a.co_pad = conv_co_pad(c.p0);
     a.act = CONV_RELU;
-    TTS_HIP(conv_launch(a, 3, B, frames, s));
+    TTS_HIP(conv_launch(a, 3, B, frames, s, &kinds[1]));
     // second projection (+ BN), residual x += inputs (layers/tacotron.py:194)
     a.in = t->p0.p;
     a.pool2 = 0;
@@ -318,7 +325,7 @@ tts_status run_cbhg(tts_tacotron* t, const Cbhg& c, const float* x, int B, int T
     a.co_pad = conv_co_pad(c.p1);
     a.act = CONV_NONE;
     a.resid = x;
-    TTS_HIP(conv_launch(a, 3, B, frames, s));
+    TTS_HIP(conv_launch(a, 3, B, frames, s, &kinds[2]));
     const float* cur = t->y.p;
     float* bufs[2] = {t->hwa.p, t->hwb.p};
     int nb = 0;
@@ -351,7 +358,7 @@ tts_status run_cbhg(tts_tacotron* t, const Cbhg& c, const float* x, int B, int T
         a.Cout = 256;
         a.co_pad = 256;
         a.act = CONV_HIGHWAY;
-        TTS_HIP(conv_launch(a, 1, B, frames, s));
+        TTS_HIP(conv_launch(a, 1, B, frames, s, &kinds[3 + i]));
         cur = bufs[nb];
         nb ^= 1;
     }
@@ -367,7 +374,7 @@ tts_status run_cbhg(tts_tacotron* t, const Cbhg& c, const float* x, int B, int T
     a.Cout = 768;
     a.co_pad = 768;
     a.act = CONV_NONE;
-    TTS_HIP(conv_launch(a, 1, B, frames, s));
+    TTS_HIP(conv_launch(a, 1, B, frames, s, &kinds[7]));
     GruSeqArgs g{};
     g.xi = t->xi.p;
     g.T = t->T;
@@ -425,7 +432,7 @@ tts_status run_gst(tts_tacotron* t, const float* style_mel, int Ts, int B, hipSt
     a.Cout = 384;
     a.co_pad = 384;
     a.act = CONV_NONE;
-    TTS_HIP(conv_launch(a, 1, B, B * H6, s));
+    TTS_HIP(conv_launch(a, 1, B, B * H6, s, &t->enc_kind[10]));
     GruSeqArgs g{};
     g.xi = t->gxi.p;
     g.T = t->gT;
@@ -1011,6 +1018,7 @@ tts_status tts_tacotron_encode(tts_tacotron* t, const int32_t* ids, const int32_
     TTS_HIP(hipMemcpyAsync(t->T, lens, sizeof(int) * B, hipMemcpyHostToDevice, s));
     const float* add1 = nullptr;
     const float* add2 = nullptr;
+    t->enc_kind[10] = -1;
     if (speaker_ids && t->spk) {  // _add_speaker_embedding (models/tacotrongst.py:81-90)
         TTS_HIP(hipMemcpyAsync(t->spk_ids, speaker_ids, sizeof(int) * B, hipMemcpyHostToDevice, s));
         TTS_HIP(launch_gather_rows(t->spk, t->spk_ids, 256, t->spk_rows.p, B, s));
@@ -1033,7 +1041,7 @@ tts_status tts_tacotron_encode(tts_tacotron* t, const int32_t* ids, const int32_
     a.Cout = 256;
     a.co_pad = 256;
     a.act = CONV_RELU;
-    TTS_HIP(conv_launch(a, 1, B, frames, s));
+    TTS_HIP(conv_launch(a, 1, B, frames, s, &t->enc_kind[0]));
     a = ConvArgs{};
     a.in = t->pre_a.p;
     a.out = t->pre_b.p;
@@ -1045,9 +1053,9 @@ tts_status tts_tacotron_encode(tts_tacotron* t, const int32_t* ids, const int32_
     a.Cout = 128;
     a.co_pad = 128;
     a.act = CONV_RELU;
-    TTS_HIP(conv_launch(a, 1, B, frames, s));
+    TTS_HIP(conv_launch(a, 1, B, frames, s, &t->enc_kind[1]));
     TTS_HIP(hipMemsetAsync(t->seq_out.p, 0, sizeof(float) * BL * 256, s));
-    if ((st = run_cbhg(t, t->enc, t->pre_b.p, B, Lmax, frames, t->seq_out.p, add1, add2, s))) return st;
+    if ((st = run_cbhg(t, t->enc, t->pre_b.p, B, Lmax, frames, t->seq_out.p, add1, add2, s, &t->enc_kind[2]))) return st;
     TTS_HIP(hipMemcpyAsync(out, t->seq_out.p, sizeof(float) * BL * 256, hipMemcpyDeviceToDevice, s));
     TTS_HIP(hipEventRecord(t->ev_out, s));
     TTS_HIP(hipStreamWaitEvent(cs, t->ev_out, 0));
@@ -1283,6 +1291,12 @@ tts_status tts_tacotron_last_timing(tts_tacotron* t, float* loop_ms, int* steps_
     TTS_CHECK(t && loop_ms && steps_run, TTS_ERR_INVALID, "null argument");
     *loop_ms = t->last_ms;
     *steps_run = t->last_steps;
+    return TTS_OK;
+}
+
+tts_status tts_tacotron_encode_last_path(tts_tacotron* t, int* kinds, int n) {
+    TTS_CHECK(t && kinds && n >= 11, TTS_ERR_INVALID, "tts_tacotron_encode_last_path needs room for 11 kinds");
+    for (int l = 0; l < 11; ++l) kinds[l] = t->enc_kind[l];
     return TTS_OK;
 }
 
