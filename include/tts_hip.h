@@ -681,6 +681,64 @@ tts_status tts_optim_step(tts_optim* o, const tts_optim_tensor* t, int n, double
                           double eps, double wd, double max_norm, double* norm64_dev, float* norm32_dev,
                           void* stream);
 
+/* ---------------------------------------------------------------- trainable LSTM
+ * The encoder's nn.LSTM(512, 256, num_layers=1, batch_first=True, bidirectional=True) as Encoder.forward
+ * runs it on a packed batch (layers/tacotron2.py:56-76), with its whole backward: one layer, one or two
+ * directions, gate rows i, f, g, o, fp32, biases on, no dropout, no projection.  Every product is an exact
+ * fp32 MFMA chain, every reduction has a fixed order and nothing is accumulated with atomics: the same
+ * operands give the same bits.  The handle owns the repacked weights and the workspaces (the input
+ * projection, dpre, the carried cell state and cell gradient, the weight-gradient partials), grown on
+ * demand; all calls on one handle must be ordered on one stream.  The reserve (what the forward keeps for
+ * the backward) belongs to the caller, so several forwards may be outstanding before their backwards.
+ * No call waits for the stream or copies to or from the host (the lengths travel as kernel arguments); a
+ * workspace that has to grow is freed and allocated again, which waits for the device that once.
+ * Every [dev] tensor must be 16-byte aligned. */
+typedef struct tts_lstm tts_lstm;
+
+/* UNSUPPORTED unless input_size and hidden_size are positive multiples of 16. */
+tts_status tts_lstm_create(int input_size, int hidden_size, int bidirectional, tts_lstm** out);
+void tts_lstm_destroy(tts_lstm* l);
+
+/* The parameters of direction d (0: weight_ih_l0 ..., 1: the _reverse set; [1] is not read without the second
+ * direction), [dev] in nn.LSTM's layout: w_ih [4H][I], w_hh [4H][H], b_ih, b_hh [4H].  Repacks them on the
+ * stream into the orders the kernels read; call it again whenever the parameters have changed. */
+tts_status tts_lstm_set_weights(tts_lstm* l, const float* const* w_ih, const float* const* w_hh,
+                                const float* const* b_ih, const float* const* b_hh, void* stream);
+
+/* Floats of the reserve a forward of this shape fills: the four activated gates and c_t of every position,
+ * and a copy of the initial cell state.  0 for a null handle or a B or Tmax <= 0. */
+int64_t tts_lstm_reserve_floats(const tts_lstm* l, int B, int Tmax);
+
+/* Replaces pack_padded_sequence + self.lstm + pad_packed_sequence (layers/tacotron2.py:68-75), and the
+ * padded calls of Encoder.inference / inference_truncated (:82, :92) with every length = Tmax.
+ *   x        [dev]  [B][Tmax][I]; rows t >= lens[b] are NOT READ
+ *   lens     [host] int32 [B], 1 <= lens[b] <= Tmax, in any order
+ *   h0, c0   [dev]  [D][B][H] or NULL (zeros)
+ *   out      [dev]  [B][Tmax][D * H] = [h_fwd(t) | h_bwd(t)]; rows t >= lens[b] are written +0.0
+ *   h_n, c_n [dev]  [D][B][H] or NULL: each direction's state after its last valid position
+ *   reserve  [dev]  tts_lstm_reserve_floats(l, B, Tmax) floats, or NULL (no backward will follow: nothing
+ *                   extra is stored, and out is bitwise the same)
+ * INVALID before any launch: a null handle, x, lens or out; weights not set; B or Tmax <= 0; a length
+ * outside [1, Tmax]; a misaligned tensor.  2 + 2 launches, then one per time step up to max(lens). */
+tts_status tts_lstm_forward(tts_lstm* l, const float* x, const int32_t* lens, int B, int Tmax, const float* h0,
+                            const float* c0, float* out, float* h_n, float* c_n, float* reserve, void* stream);
+
+/* The backward of that forward for an upstream gradient of out (autograd's walk back through
+ * layers/tacotron2.py:68-75; no gradient flows into h_n, c_n or out of h0, c0).
+ *   x, lens, B, Tmax, h0   as the forward had them; reserve, out: what it wrote
+ *   grad_out  [dev]  [B][Tmax][D * H]; rows t >= lens[b] are NOT READ
+ *   grad_x    [dev]  [B][Tmax][I] out, summed over the directions; rows t >= lens[b] are written +0.0
+ *   grad_w_ih, grad_w_hh, grad_b_ih, grad_b_hh  [2] of [dev] out in the parameters' layouts, sums over the
+ *             valid positions only ([1] is not read without the second direction)
+ * Gradients are WRITTEN, not accumulated.  grad_x, any of the four arrays and any entry of one may be NULL;
+ * that product is skipped.  The weights are those of the last tts_lstm_set_weights: they must be the
+ * forward's.  INVALID before any launch: as the forward; a null reserve, out or grad_out.  2 launches, one
+ * per time step, then at most 12. */
+tts_status tts_lstm_backward(tts_lstm* l, const float* x, const int32_t* lens, int B, int Tmax, const float* reserve,
+                             const float* out, const float* h0, const float* grad_out, float* grad_x,
+                             float* const* grad_w_ih, float* const* grad_w_hh, float* const* grad_b_ih,
+                             float* const* grad_b_hh, void* stream);
+
 const char* tts_last_error(void);
 const char* tts_version(void);
 

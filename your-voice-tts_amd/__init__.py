@@ -14,6 +14,7 @@ interface for the path:
 * ``evaluate.evaluate_batch / evaluate``      <- ``train.py`` (``evaluate``)
 * ``train.train_batch``                       <- ``train.py`` (``train``, one iteration)
 * ``optim.Adam``, ``generic_utils.weight_decay / check_update / NoamLR`` <- ``train.py:157-167``, ``utils/generic_utils.py``
+* ``layers.LSTM``, ``layers.use_device_lstm``  <- the encoder's ``nn.LSTM`` (``layers/tacotron2.py:56-76``), trainable
 
 The directory name is not a Python identifier; import with
 ``importlib.import_module("your-voice-tts_amd")``.  Importing is cheap; the native library is
@@ -24,4 +25,4 @@ import sys as _sys
 _sys.modules.setdefault("yvtts_amd", _sys.modules[__name__])
 
 __all__ = ["weights", "generic_utils", "tacotron2", "audio", "synthesis", "sharding", "data", "datasets", "losses",
-           "evaluate", "optim", "train"]
+           "evaluate", "optim", "train", "layers"]

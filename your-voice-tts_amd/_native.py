@@ -47,6 +47,8 @@ EXPORTS = (
     "tts_loss_create", "tts_loss_destroy", "tts_loss_masked", "tts_loss_bce_logits", "tts_loss_backward",
     "tts_optim_create", "tts_optim_destroy", "tts_optim_set_tensors", "tts_optim_grad_norm", "tts_optim_clip",
     "tts_optim_decay", "tts_optim_adam", "tts_optim_step",
+    "tts_lstm_create", "tts_lstm_destroy", "tts_lstm_set_weights", "tts_lstm_reserve_floats", "tts_lstm_forward",
+    "tts_lstm_backward",
     "tts_last_error", "tts_version",
 )
 
@@ -189,6 +191,15 @@ def _declare(lib):
     lib.tts_optim_decay.argtypes = [vp, OT, ctypes.c_int, D, D, vp]
     lib.tts_optim_adam.argtypes = [vp, OT, ctypes.c_int, D, D, D, D, vp]
     lib.tts_optim_step.argtypes = [vp, OT, ctypes.c_int, D, D, D, D, D, D, vp, vp, vp]
+    PP = ctypes.POINTER(vp)
+    lib.tts_lstm_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
+    lib.tts_lstm_destroy.argtypes = [vp]
+    lib.tts_lstm_destroy.restype = None
+    lib.tts_lstm_set_weights.argtypes = [vp, PP, PP, PP, PP, vp]
+    lib.tts_lstm_reserve_floats.argtypes = [vp, ctypes.c_int, ctypes.c_int]
+    lib.tts_lstm_reserve_floats.restype = ctypes.c_int64
+    lib.tts_lstm_forward.argtypes = [vp, vp, I32P, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp]
+    lib.tts_lstm_backward.argtypes = [vp, vp, I32P, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, PP, PP, PP, PP, vp]
     lib.tts_last_error.restype = ctypes.c_char_p
     lib.tts_version.restype = ctypes.c_char_p
     for name in EXPORTS:
@@ -197,7 +208,8 @@ def _declare(lib):
                           "_continue", "_basis", "_melspectrogram", "_path", "_sync", "_phases", "_teacher",
                           "_phase_state", "_pcm16", "_limits", "_analyze", "_to_mel", "_silence", "_endpoint",
                           "_segments", "_masked", "_logits", "_filter", "_resample", "_tensors", "_grad_norm",
-                          "_clip", "_decay", "_adam", "_step", "_backward", "_counters", "_rule")):
+                          "_clip", "_decay", "_adam", "_step", "_backward", "_counters", "_rule", "_weights",
+                          "_forward")):
             fn.restype = ctypes.c_int
 
 

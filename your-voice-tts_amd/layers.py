@@ -1,0 +1,262 @@
+"""Trainable layers on the device.  ``LSTM`` is a drop-in for the encoder's ``nn.LSTM(512, 256, num_layers=1,
+batch_first=True, bidirectional=True)`` (layers/tacotron2.py:56-61) in the three forms the reference calls it:
+
+* ``Encoder.forward`` (:64-76): a ``PackedSequence`` in, ``(PackedSequence, (h_n, c_n))`` out; the pack / unpack
+  glue stays torch, the recurrence, its backward through time and the weight gradients are ``tts_lstm_forward`` /
+  ``tts_lstm_backward`` (csrc/lstm_train.hip);
+* ``Encoder.inference`` (:78-83): a padded ``[B, T, I]`` tensor, every sentence at full length;
+* ``Encoder.inference_truncated`` (:85-93): the same with the ``(h_0, c_0)`` of the previous call.
+
+Parameter names, shapes and initialisation are ``nn.LSTM``'s, so state dicts load both ways.  All arithmetic is
+fp32 on fixed summation orders: the same operands give the same bits, forward and backward.  Rows at and beyond
+a sentence's length are neither read (``x``, the upstream gradient) nor left undefined (``out``, ``grad_x``: +0.0).
+``h_n`` and ``c_n`` are not differentiable and ``hx`` is a constant: an ``hx`` that requires grad raises.
+
+With grad mode off, in ``eval()`` mode (where the output does not join autograd; torch's device LSTM refuses a
+backward there too), or when neither the input nor a parameter requires grad, the forward keeps nothing for a
+backward (``last_reserve_floats`` is 0) and ``out`` has the same bits.  The weights are repacked for the kernels
+when the parameters' version counters or addresses have changed since the last call (``repacks`` counts), which
+covers ``optimizer.step()``, ``load_state_dict`` and ``.to()``.
+
+Without a GPU a call raises the package's "no GPU" RuntimeError; there is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+
+import torch
+from torch import nn
+from torch.autograd.function import once_differentiable
+from torch.nn.utils.rnn import PackedSequence, pack_padded_sequence, pad_packed_sequence
+
+from . import _native
+
+_NAMES = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _ptr_pair(ts):
+    """[2] of device pointers (None -> NULL), or NULL when every entry is None."""
+    if all(t is None for t in ts):
+        return None
+    arr = (ctypes.c_void_p * 2)()
+    for i, t in enumerate(ts):
+        arr[i] = t.data_ptr() if t is not None else None
+    return arr
+
+
+def _aligned(t):
+    """t contiguous and 16-byte aligned (a copy where it is not)."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
+class _LSTMFunction(torch.autograd.Function):
+    """forward(x [B, T, I], module, lens (host ints), h0, c0, *parameters) -> (out, h_n, c_n).  The parameters ride
+    along so that autograd asks for their gradients; the kernels read the module's repacked copies."""
+
+    @staticmethod
+    def forward(ctx, x, module, lens, h0, c0, *params):
+        out, h_n, c_n, reserve = module._run_forward(x, lens, h0, c0, True)
+        ctx.save_for_backward(x, out, reserve, *([] if h0 is None else [h0]))
+        ctx.module, ctx.lens, ctx.has_h0 = module, lens, h0 is not None
+        ctx.versions = module._key()
+        ctx.mark_non_differentiable(h_n, c_n)
+        return out, h_n, c_n
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out, _grad_h, _grad_c):
+        x, out, reserve, *h0 = ctx.saved_tensors
+        m = ctx.module
+        if m._key() != ctx.versions:
+            raise RuntimeError("layers.LSTM: the parameters were modified between this forward and its backward")
+        need = ctx.needs_input_grad
+        grads = m._run_backward(x, ctx.lens, reserve, out, h0[0] if ctx.has_h0 else None, grad_out, need[0], need[5:])
+        return (grads[0], None, None, None, None) + tuple(grads[1:])
+
+
+class LSTM(nn.Module):
+    """``nn.LSTM(input_size, hidden_size, num_layers=1, bias=True, batch_first=True, bidirectional=...)`` on the
+    device.  ``last_reserve_floats``: the size of the reserve the last forward kept (0: none); ``repacks``: how
+    often the weights were repacked."""
+
+    def __init__(self, input_size, hidden_size, num_layers=1, bias=True, batch_first=False, dropout=0.0,
+                 bidirectional=False, proj_size=0, device=None, dtype=None):
+        super().__init__()
+        for ok, what in ((num_layers == 1, "num_layers != 1"), (bias, "bias=False"),
+                         (batch_first, "batch_first=False"), (dropout == 0, "dropout"), (proj_size == 0, "proj_size"),
+                         (dtype in (None, torch.float32), "a dtype other than float32"),
+                         (input_size > 0 and input_size % 16 == 0, "an input_size that is no multiple of 16"),
+                         (hidden_size > 0 and hidden_size % 16 == 0, "a hidden_size that is no multiple of 16")):
+            if not ok:
+                raise NotImplementedError(f"layers.LSTM does not implement {what}")
+        self.input_size, self.hidden_size, self.bidirectional = input_size, hidden_size, bool(bidirectional)
+        self.num_layers, self.bias, self.batch_first, self.dropout, self.proj_size = 1, True, True, 0.0, 0
+        G = 4 * hidden_size
+        for suffix in ("", "_reverse")[:self.num_directions]:
+            for name, shape in zip(_NAMES, ((G, input_size), (G, hidden_size), (G,), (G,))):
+                self.register_parameter(name + suffix, nn.Parameter(torch.empty(shape, device=device)))
+        self.reset_parameters()
+        self._h = None
+        self._packed_key = None
+        self.repacks = 0
+        self.last_reserve_floats = 0
+
+    @property
+    def num_directions(self):
+        return 2 if self.bidirectional else 1
+
+    def reset_parameters(self):  # nn.LSTM's: U(-1 / sqrt(H), 1 / sqrt(H)) on every parameter
+        k = 1.0 / math.sqrt(self.hidden_size)
+        for p in self.parameters():
+            nn.init.uniform_(p, -k, k)
+
+    def flatten_parameters(self):  # (layers/tacotron2.py:70: nothing to flatten here)
+        pass
+
+    def extra_repr(self):
+        return f"{self.input_size}, {self.hidden_size}, batch_first=True, bidirectional={self.bidirectional}"
+
+    def __del__(self):
+        try:
+            if self._h is not None:
+                self._h[0].tts_lstm_destroy(self._h[1])
+        except Exception:
+            pass
+
+    # ------------------------------------------------------------------ the handle and its weights
+    def _params(self):
+        return [getattr(self, n + s) for s in ("", "_reverse")[:self.num_directions] for n in _NAMES]
+
+    def _key(self):
+        return tuple((p.data_ptr(), p._version) for p in self._params())
+
+    def _handle(self):
+        lib = _native.lib()  # raises without a GPU / library: no CPU fallback
+        if self._h is None:
+            h = ctypes.c_void_p()
+            _native.check(lib.tts_lstm_create(self.input_size, self.hidden_size, int(self.bidirectional),
+                                              ctypes.byref(h)), "tts_lstm_create")
+            self._h = (lib, h)
+        return self._h
+
+    def _sync_weights(self):
+        lib, h = self._handle()
+        key = self._key()
+        if key == self._packed_key:
+            return
+        ps = self._params()
+        for p in ps:
+            if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or p.data_ptr() % 16:
+                raise ValueError("layers.LSTM: parameters must be contiguous 16-byte aligned CUDA float32 tensors")
+        per = [_ptr_pair([ps[d * 4 + k] for d in range(self.num_directions)] + [None] * (2 - self.num_directions))
+               for k in range(4)]
+        _native.check(lib.tts_lstm_set_weights(h, *per, _native.stream_handle()), "tts_lstm_set_weights")
+        self._packed_key = key
+        self.repacks += 1
+
+    # ------------------------------------------------------------------ the two calls
+    def _run_forward(self, x, lens, h0, c0, want_reserve):
+        lib, h = self._handle()
+        self._sync_weights()
+        B, T, _ = x.shape
+        D, H = self.num_directions, self.hidden_size
+        x = _aligned(x.detach())
+        out = torch.empty(B, T, D * H, dtype=torch.float32, device=x.device)
+        h_n = torch.empty(D, B, H, dtype=torch.float32, device=x.device)
+        c_n = torch.empty_like(h_n)
+        reserve = None
+        if want_reserve:
+            reserve = torch.empty(lib.tts_lstm_reserve_floats(h, B, T), dtype=torch.float32, device=x.device)
+        self.last_reserve_floats = 0 if reserve is None else reserve.numel()
+        _native.check(lib.tts_lstm_forward(h, _ptr(x), _native.i32_array(lens), B, T, _ptr(h0), _ptr(c0), _ptr(out),
+                                           _ptr(h_n), _ptr(c_n), _ptr(reserve), _native.stream_handle()),
+                      "tts_lstm_forward")
+        return out, h_n, c_n, reserve
+
+    def _run_backward(self, x, lens, reserve, out, h0, grad_out, need_x, need_params):
+        lib, h = self._handle()
+        B, T, _ = x.shape
+        D = self.num_directions
+        x = _aligned(x.detach())
+        grad_out = _aligned(grad_out)
+        grad_x = torch.empty_like(x) if need_x else None
+        ps = self._params()
+        gp = [torch.empty_like(p) if need else None for p, need in zip(ps, need_params)]
+        per = [_ptr_pair([gp[d * 4 + k] for d in range(D)] + [None] * (2 - D)) for k in range(4)]
+        _native.check(lib.tts_lstm_backward(h, _ptr(x), _native.i32_array(lens), B, T, _ptr(reserve), _ptr(out),
+                                            _ptr(h0), _ptr(grad_out), _ptr(grad_x), *per, _native.stream_handle()),
+                      "tts_lstm_backward")
+        return [grad_x] + gp
+
+    def _call(self, x, lens, hx):
+        if x.dim() != 3 or x.shape[2] != self.input_size:
+            raise ValueError(f"expected input [B, T, {self.input_size}], got {tuple(x.shape)}")
+        if not x.is_cuda:
+            _native.lib()  # the "no GPU" error where there is none
+            raise RuntimeError("layers.LSTM: the input must be a CUDA tensor (there is no CPU path)")
+        if x.dtype != torch.float32:
+            raise ValueError(f"layers.LSTM: the input must be float32, got {x.dtype}")
+        B, T, _ = x.shape
+        lens = [int(v) for v in lens]
+        if len(lens) != B or min(lens) < 1 or max(lens) > T:
+            raise ValueError(f"lengths {lens} do not fit a batch of {B} with {T} positions")
+        h0 = c0 = None
+        if hx is not None:
+            h0, c0 = hx
+            if h0.requires_grad or c0.requires_grad:
+                raise NotImplementedError("layers.LSTM: hx is a constant; gradients with respect to it are not "
+                                          "implemented")
+            shape = (self.num_directions, B, self.hidden_size)
+            if tuple(h0.shape) != shape or tuple(c0.shape) != shape:
+                raise ValueError(f"expected hx of two {shape} tensors, got {tuple(h0.shape)}, {tuple(c0.shape)}")
+            h0, c0 = (_aligned(t.detach().to(x.device, torch.float32)) for t in (h0, c0))
+        params = self._params()
+        if not (self.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))):
+            return self._run_forward(x, lens, h0, c0, False)[:3]
+        return _LSTMFunction.apply(x, self, lens, h0, c0, *params)
+
+    def forward(self, input, hx=None):
+        if isinstance(input, PackedSequence):
+            # padded in the caller's order, which is also the order of hx and of the states nn.LSTM returns
+            x, lengths = pad_packed_sequence(input, batch_first=True)
+            out, h_n, c_n = self._call(x, lengths.tolist(), hx)
+            packed = pack_padded_sequence(out, lengths, batch_first=True, enforce_sorted=input.sorted_indices is None)
+            return packed, (h_n, c_n)
+        out, h_n, c_n = self._call(input, [input.shape[1]] * input.shape[0], hx)
+        return out, (h_n, c_n)
+
+
+    def lstm(self, x, lengths, hx=None):
+        """The functional form on padded input: ``x [B, T, I]`` with ``lengths`` in any order -> ``(out [B, T, D * H]``
+        with +0.0 past each length, ``(h_n, c_n))``; no packing on either side."""
+        out, h_n, c_n = self._call(x, torch.as_tensor(lengths).reshape(-1).tolist(), hx)
+        return out, (h_n, c_n)
+
+
+def lstm(x, lengths, module, hx=None):
+    """``module.lstm(x, lengths, hx)`` for a ``layers.LSTM`` module."""
+    return module.lstm(x, lengths, hx)
+
+
+def use_device_lstm(model):
+    """Swap ``model.encoder.lstm`` (the reference's ``nn.LSTM``, layers/tacotron2.py:56-61) for a ``layers.LSTM``
+    that carries the same weights on the same device; returns the model.  Build the optimizer afterwards: the
+    parameters are new tensors."""
+    old = model.encoder.lstm
+    if isinstance(old, LSTM):
+        return model
+    new = LSTM(old.input_size, old.hidden_size, num_layers=old.num_layers, bias=old.bias,
+               batch_first=old.batch_first, dropout=old.dropout, bidirectional=old.bidirectional,
+               proj_size=getattr(old, "proj_size", 0))
+    new.load_state_dict(old.state_dict())
+    p = next(old.parameters())
+    new.to(p.device)
+    new.train(old.training)
+    model.encoder.lstm = new
+    return model

@@ -97,15 +97,23 @@ class _Engine:
                       "tts_optim_clip" if clip else "tts_optim_grad_norm")
         return n64, n32, host.value
 
+    @staticmethod
+    def _written(rows):
+        """The library wrote the parameters through their pointers: their version counters say so, as after any
+        in-place torch op (layers.LSTM keys its repacked weights on them)."""
+        torch.autograd.graph.increment_version([r[0] for r in rows])
+
     def decay(self, rows, lr, wd):
         lib, h, table, n, _ = self._prepare(rows)
         _native.check(lib.tts_optim_decay(h, table, n, float(lr), float(wd), _native.stream_handle()),
                       "tts_optim_decay")
+        self._written(rows)
 
     def adam(self, rows, lr, betas, eps):
         lib, h, table, n, _ = self._prepare(rows)
         _native.check(lib.tts_optim_adam(h, table, n, float(lr), float(betas[0]), float(betas[1]), float(eps),
                                          _native.stream_handle()), "tts_optim_adam")
+        self._written(rows)
 
     def step(self, rows, lr, betas, eps, wd, max_norm):
         lib, h, table, n, device = self._prepare(rows)
@@ -113,6 +121,7 @@ class _Engine:
         _native.check(lib.tts_optim_step(h, table, n, float(lr), float(betas[0]), float(betas[1]), float(eps),
                                          float(wd), float(max_norm), ctypes.c_void_p(n64.data_ptr()),
                                          ctypes.c_void_p(n32.data_ptr()), _native.stream_handle()), "tts_optim_step")
+        self._written(rows)
         return n64, n32
 
 

@@ -5,7 +5,9 @@ speaker ids, the grouped stop targets, ``scheduler.step()``, ``zero_grad()``, th
 forward, the three criteria of train.py:462-465 (``losses``: the values are bitwise those ``evaluate_batch``
 reports for the same outputs), ``loss.backward()``, and the update: ``optim.Adam.step_fused`` when the optimizer
 is the package's, ``weight_decay(); check_update(); optimizer.step()`` otherwise.  Forward and backward of the
-*model* stay the caller's torch; the criteria's backward is ``tts_loss_backward``.
+*model* stay the caller's torch, except for the encoder's LSTM once ``layers.use_device_lstm(model)`` has swapped
+it for ``layers.LSTM`` (``tts_lstm_forward`` / ``tts_lstm_backward``; build the optimizer after the swap); the
+criteria's backward is ``tts_loss_backward``.
 
 Not part of it: the epoch loop, the logging, checkpoints, ``reduce_tensor`` across ranks and the diagnostic
 audio of train.py:171-260.
