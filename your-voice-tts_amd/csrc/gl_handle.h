@@ -139,7 +139,8 @@ struct tts_gl {
     int last_path = TTS_GL_PATH_UNFUSED;
     tts::DeviceBuf<unsigned> flags;  // persistent loop: the workgroups' XCD table
     tts::DeviceBuf<tts::gran_t> pgr;  // persistent loop: two granule slots
-    std::vector<signed char> gather_fit;  // by frame count: the persistent gather's layout holds (-1: unknown)
+    std::vector<signed char> gather_fit;  // by frame count: the persistent loop's contributor relation is
+                                          // symmetric and its gather layout holds (-1: unknown)
     int* pstatus = nullptr;     // [dev] status of the persistent loop
     int* host_status = nullptr; // pinned coherent: [0] status of the last persistent loop, [1] its sequence
     int seq = 0;                // pipeline mode: the sequence the last persistent run's overlap-add sets

@@ -27,6 +27,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -1600,10 +1601,14 @@ bool gl_fused_path(const tts_gl* g, int B, int Fmax) {
 // The persistent loop overwrites a frame's ping-pong slot once its own contributors have moved on:
 // safe when every reader of a frame is one of its contributors.  Frame f reads the signal at the
 // reflected positions R(W_f), W_f = [f hop - win/2, f hop + win/2) (centred STFT frames), and its
-// contributors are the frames fi whose windows W_fi hold one of them.  While one reflection
-// suffices (win/2 < hop (F - 1)), R maps the part of W_f outside [0, N) into W_f's own part inside,
-// so R(W_f) = W_f n [0, N) and "f reads fi" <=> W_f n W_fi n [0, N) != {} is symmetric.  Shorter
-// sentences are checked by brute force (host copy of the kernels' index maps).
+// contributors are the frames fi whose windows W_fi hold one of them.  Between two frames whose
+// windows lie inside [0, N) "f reads fi" <=> W_f n W_fi != {} is symmetric.  A frame whose window
+// reaches a sentence edge reads R(W_f), which is not W_f n [0, N): position -win/2 reflects to
+// win/2, one past W_0, and N + win/2 - 1 to N - win/2 - 1, one before W_(F-1); whether a frame that
+// W_f itself does not meet contributes there depends on the geometry (at win = 4 hop, win even,
+// frame 0 reads frame 4 and frame F - 1 reads frame F - 5 from six frames up, and neither is read
+// back; at 1102 / 275 the same positions fall to frames the window meets anyway).  So every frame
+// count is checked by brute force (host copy of the kernels' index maps).
 int reflect_host(int p, int N) {
     if ((unsigned)p < (unsigned)N) return p;
     if (N == 1) return 0;
@@ -1629,13 +1634,33 @@ bool for_contributors(const Geo& g, int f, int F, Fn fn) {
     }
     return true;
 }
+// Rows of the relation are built for the frames near either end only: the frames whose window reaches
+// an edge (at most win / (2 hop) + 1 per end) and the 2 OLA_MAX frames next to them, all frames of a
+// short sentence.  Any other pair of frames is symmetric by the argument above, and a frame outside
+// the rows reads nothing beyond OLA_MAX frames from itself, so an edge frame that reads it is not read back.
 bool contrib_symmetric(const Geo& g, int F) {
-    std::vector<char> c((size_t)F * F, 0);
+    const int N = g.hop * (F - 1);
+    auto edge = [&](int f) {
+        return f * g.hop + g.woff - NFFT / 2 < 0 || f * g.hop + g.woff + g.win - 1 - NFFT / 2 >= N;
+    };
+    const int K = g.win / (2 * g.hop) + 2 + 2 * OLA_MAX;  // rows per end
+    std::vector<int> rows;
     for (int f = 0; f < F; ++f)
-        for_contributors(g, f, F, [&](int, int, int fi) { return c[(size_t)f * F + fi] = 1; });
-    for (int f = 0; f < F; ++f)
-        for (int fi = 0; fi < F; ++fi)
-            if (c[(size_t)f * F + fi] != c[(size_t)fi * F + f]) return false;
+        if (f < K || f >= F - K) rows.push_back(f);
+    std::vector<int> row_of(F, -1);
+    for (size_t r = 0; r < rows.size(); ++r) row_of[rows[r]] = (int)r;
+    std::vector<char> c(rows.size() * (size_t)F, 0);
+    for (size_t r = 0; r < rows.size(); ++r)
+        for_contributors(g, rows[r], F, [&](int, int, int fi) { return c[r * F + fi] = 1; });
+    for (size_t r = 0; r < rows.size(); ++r)
+        for (int fi = 0; fi < F; ++fi) {
+            const char reads = c[r * F + fi];
+            if (row_of[fi] >= 0) {
+                if (reads != c[(size_t)row_of[fi] * F + rows[r]]) return false;
+            } else if (reads && edge(rows[r])) {
+                return false;
+            }
+        }
     return true;
 }
 // The persistent loop's gather layout for a sentence of F frames (gl_persistent_kernel): every
@@ -2025,14 +2050,11 @@ bool gl_persistent_path(tts_gl* g, int B, int Fmax, int frames_total, int iters)
     if (!(gl_fused_path(g, B, Fmax) && iters > 0 && iters < (1 << 14) && frames_total <= 512 && g->tmo > 0 &&
           !env_is("TTS_RESIDENT", '0')))
         return false;
-    // every frame count the run may have (a speculative run knows only the upper bound Fmax)
-    for (int F = 2; F <= Fmax; ++F) {
-        if (2 * g->g.hop * (F - 1) > g->g.win + 2) break;  // one reflection suffices: symmetric from here on (above)
-        if (!contrib_symmetric(g->g, F)) return false;
-    }
+    // every frame count the run may have (a speculative run knows only the upper bound Fmax): a
+    // geometry or length the loop is not safe for takes the fused loop instead
     if ((int)g->gather_fit.size() <= Fmax) g->gather_fit.resize(Fmax + 1, -1);
     for (int F = 2; F <= Fmax; ++F) {
-        if (g->gather_fit[F] < 0) g->gather_fit[F] = gather_fits(g->g, F) ? 1 : 0;
+        if (g->gather_fit[F] < 0) g->gather_fit[F] = contrib_symmetric(g->g, F) && gather_fits(g->g, F) ? 1 : 0;
         if (!g->gather_fit[F]) return false;
     }
     return true;
@@ -2049,7 +2071,10 @@ tts_status gl_collect(tts_gl* g) {
         TTS_HIP(spin_word(g->host_status + 1, g->seq, g->seq_stream));
     }
     if (g->last_persistent)
-        TTS_CHECK(g->host_status[0] == 0, TTS_ERR_HIP, "persistent Griffin-Lim: a hand-off wait timed out (internal error)");
+        // (the kernel's code: 1 a gather wait, 2 the placement table, 4 / 5 / 6 a layout the host should have refused)
+        TTS_CHECK(g->host_status[0] == 0, TTS_ERR_HIP,
+                  "persistent Griffin-Lim: a hand-off wait timed out (internal error, code " +
+                      std::to_string(g->host_status[0]) + ")");
     return TTS_OK;
 }
 
