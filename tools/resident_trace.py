@@ -27,8 +27,11 @@ weights = importlib.import_module("your-voice-tts_amd.weights")
 # events 12, 13 (both forms): the loop-top work done on wave 0 / wave 3, ahead of the pre1 poll
 EV_TOP = ("looptop_w0", "looptop_w3", "unused", "unused")
 # event 14 (synthesis form): the next step's attention operand loads issued (wave 6, end of the step)
+# event 11 (synthesis form): on a stop CU the continue flag published (wave 3, end of the step); on
+# every other CU the pre1 rows gathered, by wave 0 on the CUs of even rank and wave 1 on the odd
+# event 15 (synthesis form): the previous step's continue flag gathered (wave 2)
 EV_SYN = ("P1", "B1", "hatt_pub", "B3", "B4", "hdec_pub", "B6", "pre1_pub", "part_pub", "part_gathered", "att_A2",
-          "unused") + EV_TOP[:2] + ("operands_issued", "unused")
+          "rows_gathered|flag_pub") + EV_TOP[:2] + ("operands_issued", "flag_gathered")
 EV_GEN = EV_SYN[:8] + ("q_pub", "unused", "unused", "ctx_pub") + EV_TOP
 STOP_CUS = 8  # workgroups 0-7 are rank 0 of their XCD (the stop CUs) under round-robin placement
 
@@ -54,6 +57,14 @@ last = {"hatt_pub": collections.Counter(), "hdec_pub": collections.Counter(), "p
 period, edge_p1 = [], []
 # the loop top of step t: from this CU's pre1 publish of step t-1 (wave 0) to the stamps ahead of
 # the pre1 poll; P1 after the step's first P1; the stop CUs against the rest
+# the continue flag against the pre1 rows (synthesis form), us: at the publishers, the flag's
+# publish after the XCD's last row (wave 0's rows: the one stamped) and after the stop CU's own;
+# at the consumers (the CUs that are no stop CU), the flag's gather after the rows' gather on the
+# same CU, and both against P1.  XCD = workgroup % 8, rank = workgroup // 8 (round-robin placement)
+flag = {k: [] for k in ("last_row_pub_to_flag_pub", "stop_cu_row_pub_to_flag_pub", "rows_w0_gathered_to_flag_gathered",
+                        "rows_w1_gathered_to_flag_gathered", "rows_gathered_to_P1", "flag_gathered_to_P1")}
+flag_later = []
+xcd, rk = np.arange(256) % 8, np.arange(256) // 8
 top = {k: [] for k in ("looptop_w0_rest", "looptop_w0_stop", "looptop_w3_rest", "looptop_w3_stop", "P1_rest", "P1_stop")}
 mmm = lambda v: (v.min(), np.median(v), v.max())
 for t in steps:
@@ -66,7 +77,19 @@ for t in steps:
         top[f"looptop_{w}_stop"].append(mmm(d[:STOP_CUS]))
     top["P1_rest"].append(mmm(tr[STOP_CUS:, t, 0] - t0))
     top["P1_stop"].append(mmm(tr[:STOP_CUS, t, 0] - t0))
+    if not args.nomask:
+        fp = tr[:STOP_CUS, t - 1, 11]  # step t-1's flag: step t's P1 (parent) or B1 waits for it
+        flag["last_row_pub_to_flag_pub"].append(mmm(np.array([fp[x] - tr[xcd == x, t - 1, 7].max() for x in range(8)])))
+        flag["stop_cu_row_pub_to_flag_pub"].append(mmm(fp - tr[:STOP_CUS, t - 1, 7]))
+        d = tr[:, t, 15] - tr[:, t, 11]
+        flag["rows_w0_gathered_to_flag_gathered"].append(mmm(d[(rk > 0) & (rk % 2 == 0)]))
+        flag["rows_w1_gathered_to_flag_gathered"].append(mmm(d[rk % 2 == 1]))
+        flag["rows_gathered_to_P1"].append(mmm((tr[:, t, 0] - tr[:, t, 11])[STOP_CUS:]))
+        flag["flag_gathered_to_P1"].append(mmm((tr[:, t, 0] - tr[:, t, 15])[STOP_CUS:]))
+        flag_later.append(float((d[STOP_CUS:] > 0).mean()))
     for k, name in enumerate(EV):
+        if name == "rows_gathered|flag_pub":  # (two meanings: reported above)
+            continue
         v = tr[:, t, k]
         v = v[v > 0]
         if v.size == 0:  # (an event this form does not record)
@@ -80,6 +103,9 @@ rec = {"us_per_step_trace": float(np.median(period)),
        "loop_top_us(min,median,max)": {k: [round(float(x), 2) for x in np.median(np.array(v), 0)] for k, v in top.items()},
        "events_rel_step_start_us(min,median,max)": {k: [round(float(x), 2) for x in np.median(np.array(v), 0)]
                                                     for k, v in rel.items() if v},
+       "flag_vs_rows_us(min,median,max)": {k: [round(float(x), 2) for x in np.median(np.array(v), 0)]
+                                           for k, v in flag.items() if v},
+       "flag_gathered_after_rows_share_of_cus": round(float(np.mean(flag_later)), 3) if flag_later else None,
        "last_cu": {k: v.most_common(6) for k, v in last.items()},
        "phases": ph}
 print(json.dumps(rec, indent=1))

@@ -147,7 +147,9 @@ constexpr int RES_PHASES = 16;
 // (P1, B1, h_att published, B3, B4, h_dec published, B6, pre1 row published; synthesis form: partials
 // published, partials gathered, A2 (candidate energies); general form: query row published [8],
 // context published [11]; both forms: loop-top work done on wave 0 [12] and on wave 3 [13], ahead
-// of the pre1 poll; synthesis form: next step's attention operands issued, wave 6 [14]; [15] unused)
+// of the pre1 poll; synthesis form: next step's attention operands issued, wave 6 [14]; the continue
+// flag published on a stop CU, wave 3, and on every other CU the pre1 rows gathered, wave 0 on the
+// CUs of even rank and wave 1 on the odd [11]; the previous step's continue flag gathered, wave 2 [15])
 constexpr int RES_TRACE_STEPS = 64, RES_TRACE_EV = 16;
 constexpr size_t RES_PROF_LL = 2 * RES_PHASES + (size_t)RES_CUS * RES_TRACE_STEPS * RES_TRACE_EV;
 

@@ -5,7 +5,9 @@
 //   1. loop top: general form, both LSTMs' recurrent partials over [ctx_{t-1} | h_att_{t-1}] and
 //      h_dec_{t-1} while pre1 is in flight; synthesis form: nothing, its partials ran inside the
 //      device-wide waits of steps 4 and 10 (step 0's attention partial ahead of the loop)
-//   2. wave 0: wait pre1_t (+ continue flag), prenet-2 row c, publish; gather the 256 rows
+//   2. waves 0-1: wait pre1_t (general form: wave 2 the continue flag); prenet-2 row c, publish;
+//      gather the 256 rows; synthesis form: wave 2 sweeps the previous step's continue flag behind
+//      its prenet-2 row and the loop ends after B1 (the flag leaves the stop CU behind every row)
 //   3. prenet part, row sums, LSTM cell of units 4c..4c+3, publish h_att_t   (tacotron2.py:195-197)
 //   4. synthesis form: decoder-LSTM partial over h_dec_{t-1} (LDS weights) as the first-poll delay;
 //      gather h_att_t; 5. four query rows of the XCD's copy (common_layers.py:179); synthesis form:
@@ -19,7 +21,8 @@
 //      the first-poll delay, carried to step 3 of t+1; gather h_dec_t (the prenet-1 row weights of
 //      step 11 in flight from the XCD's L2);
 //  11. every wave: one folded prenet-1 row of this XCD's copy -> XCD-local publish; the XCD's
-//      stop CU (rank 0), wave 3: the stop row -> sigmoid + stop rule -> XCD-local continue flag
+//      stop CU (rank 0), wave 3: the stop row (synthesis form: in a pass of its own behind the
+//      publish) -> sigmoid + stop rule -> XCD-local continue flag
 //      (tacotron2.py:214-224, 256-277).  Mel row c of step t is written by wave 4 during step
 //      t+1's h_att gather (after the loop for the last step).
 //  12. synthesis form, waves 3-7 (no poll of theirs before step t+1's h_att gather): step t+1's
@@ -65,6 +68,10 @@ __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast
 __device__ __forceinline__ void pin4(float4& a, float4& b, float4& c, float4& d) {
     asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w), "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.w), "+v"(c.x),
                  "+v"(c.y), "+v"(c.z), "+v"(c.w), "+v"(d.x), "+v"(d.y), "+v"(d.z), "+v"(d.w));
+}
+__device__ __forceinline__ void pin3(float4& a, float4& b, float4& c) {
+    asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w), "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.w), "+v"(c.x),
+                 "+v"(c.y), "+v"(c.z), "+v"(c.w));
 }
 // Sums over each half-wave (lanes 0-31, 32-63) by DPP row scans: the totals land in lanes 31
 // and 63 (other lanes hold partial scans).  No LDS round trip per level.
@@ -548,7 +555,7 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         // 1) general form: both LSTMs' recurrent partials while pre1 is in flight.  The synthesis
         //    form formed them inside the previous device-wide waits (steps 4 and 10): its loop top
         //    holds nothing but the pre1 poll, so a stop CU's stop row and rule (step 11), which
-        //    precede it on wave 3, are absorbed by the pre1 edge's wait
+        //    precede it on wave 3, run while the other waves wait for the pre1 rows
         float acc_a, acc_d;
         if constexpr (GEN) {
             RES_ATT_PARTIAL(acc_a)
@@ -560,8 +567,13 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         if (tid == 192) { RES_EV(t, 13) }
         // 2) prenet layer 2: wave 0 gathers this XCD's pre1_t (+ the previous step's continue flag);
         //    every wave computes its row of this XCD's copy, publishes it XCD-locally; wave 0 gathers
-        // (waves 0, 1: the 256 rows as pairs; wave 2, lane 0: the flag)
-        if (wave < 3) {
+        // (waves 0, 1: the 256 rows as pairs; wave 2, lane 0: the flag.  The synthesis form's P1
+        // waits for the rows alone: the flag leaves the stop CU behind the stop row and the rule,
+        // 0.4 us after the XCD's last row (traced), and is 1 on all steps but the last, so its
+        // wave 2 sweeps it behind its prenet-2 row, one XCD-local edge later, and the loop ends
+        // after B1)
+        constexpr bool DEFER = !GEN;
+        if (wave < (DEFER ? 2 : 3)) {
             const int gp = s_1 + ((t & 1) ^ 1) * GR_TOTAL;
             bool ok = true;
             if (t == 0) {
@@ -576,9 +588,15 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
                     ok = sweep_pair(rg, gp + 2 * pk, true, EP6, p0, p1, tmo);
                     xp1[2 * pk] = p0;
                     xp1[2 * pk + 1] = p1;
+                    if constexpr (!GEN) {  // rows gathered: wave 0 on the CUs of even rank, wave 1 on the odd
+                        if (lane == 0 && wave == (rank & 1) && !stop_cu) { RES_EV(t, 11) }
+                    }
                 } else {
                     ok = sweep_pair(rg, lane == 0 ? gp + PRE : -1, false, EP6, p0, p1, tmo);
                     if (lane == 0 && ok && p0 == 0.f) flags[0] = 1;
+                    if constexpr (!GEN) {
+                        if (lane == 0) { RES_EV(t, 15) }
+                    }
                 }
             }
             RES_MARK(0);
@@ -586,7 +604,10 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         }
         __syncthreads();  // P1
         if (tid == 0) { RES_EV(t, 0) }
-        if (flags[0] | flags[1]) break;
+        // (the synthesis form runs the prenet-2 edge of a step that does not exist once, on the
+        // ending step: it touches xp1, xpre and this step's prenet-2 granules, which nothing reads
+        // afterwards, and its gather completes, every CU of the XCD having read the same flag)
+        if (DEFER ? flags[1] : (flags[0] | flags[1])) break;
         {
             const float4 x = ld4(xp1 + lane * 4);
             u64* gx = gxs;
@@ -595,6 +616,18 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
                 if (lane == 0) publish_xcd(gx + r0, E + 1, fmaxf(s0 + bp2, 0.f));
             }
             RES_MARK(1);
+            if constexpr (DEFER) {
+                // the previous step's continue flag (same granule, tag and bound as ahead of P1)
+                if (wave == 2 && t > 0) {
+                    float p0 = 0.f, p1 = 0.f;
+                    const bool ok = sweep_pair(rg, lane == 0 ? s_1 + ((t & 1) ^ 1) * GR_TOTAL + PRE : -1, false, EP6, p0, p1, tmo);
+                    if (lane == 0) {
+                        if (!ok) { flags[1] = 1; fail(a.status, 1, t); }
+                        else if (p0 == 0.f) flags[0] = 1;
+                        RES_EV(t, 15)
+                    }
+                }
+            }
             if (wave < 2) {
                 for (int i = 0; i < a.sleep_pre2; ++i) __builtin_amdgcn_s_sleep(4);
                 float q0, q1;
@@ -606,7 +639,7 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         }
         __syncthreads();  // B1
         if (tid == 0) { RES_EV(t, 1) }
-        if (flags[1]) break;
+        if (DEFER ? (flags[0] | flags[1]) : flags[1]) break;
         RES_MARK(2);
         // 3) prenet part, cell
 #pragma unroll
@@ -1168,22 +1201,40 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         long long m0 = 0;  // prenet-1 / mel / stop row phase timing (wave 2, lane 0)
         if (prof && tid == 128) m0 = (long long)wall_clock64();
         // 11) this wave's folded prenet-1 row of step t+1 (XCD copy) and, on the stop CU's wave 3,
-        //     the stop row in the same pass
+        //     the stop row: the general form in the same pass; the synthesis form in a pass of its
+        //     own behind the publish (the same six products in the same order), so that the row the
+        //     XCD's 32 CUs wait for leaves with the others
         {
             const bool stw = stop_cu && wave == 3;
             const float4* wsr = reinterpret_cast<const float4*>(rm) + 6 * 64 + lane;
             float s = 0.f, ss = 0.f;
+            if constexpr (!GEN) {
+                // two rounds of three chunks of [h_dec | ctx], a round's LDS reads in flight together
+                // (left to itself the compiler waits for each read before the next: six round trips
+                // on every CU's chain; all six at once spill registers)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float4 x = ld4(xh_dec + i * 256 + lane * 4);
-                s = dot4(w1[i], x, s);
-                if (stw) ss = dot4(wsr[i * 64], x, ss);
-            }
+                for (int h = 0; h < 6; h += 3) {
+                    float4 xx[3];
 #pragma unroll
-            for (int i = 4; i < 6; ++i) {
-                const float4 x = ld4(xctx + (i - 4) * 256 + lane * 4);
-                s = dot4(w1[i], x, s);
-                if (stw) ss = dot4(wsr[i * 64], x, ss);
+                    for (int j = 0; j < 3; ++j)
+                        xx[j] = h + j < 4 ? ld4(xh_dec + (h + j) * 256 + lane * 4) : ld4(xctx + (h + j - 4) * 256 + lane * 4);
+                    pin3(xx[0], xx[1], xx[2]);
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) s = dot4(w1[h + j], xx[j], s);
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float4 x = ld4(xh_dec + i * 256 + lane * 4);
+                    s = dot4(w1[i], x, s);
+                    if (stw) ss = dot4(wsr[i * 64], x, ss);
+                }
+#pragma unroll
+                for (int i = 4; i < 6; ++i) {
+                    const float4 x = ld4(xctx + (i - 4) * 256 + lane * 4);
+                    s = dot4(w1[i], x, s);
+                    if (stw) ss = dot4(wsr[i * 64], x, ss);
+                }
             }
             s = wave_sum_dpp(s);
             u64* g1 = g1s;
@@ -1194,6 +1245,23 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
                 if (xlog) a.pre1[r0] = p;  // the next step's layer 1 (continuous mode reads it)
             }
             if (stw) {
+                if constexpr (!GEN) {
+                    asm volatile("" ::: "memory");  // (the stop row's LDS reads stay behind the publish)
+#pragma unroll 1
+                    for (int h = 0; h < 6; h += 3) {
+                        float4 wv[3], xx[3];
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) {
+                            const int i = h + j;
+                            wv[j] = wsr[i * 64];
+                            xx[j] = i < 4 ? ld4(xh_dec + i * 256 + lane * 4) : ld4(xctx + (i - 4) * 256 + lane * 4);
+                        }
+                        pin3(wv[0], wv[1], wv[2]);
+                        pin3(xx[0], xx[1], xx[2]);
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) ss = dot4(wv[j], xx[j], ss);
+                    }
+                }
                 ss = wave_sum_dpp(ss);
                 if (lane == 0) {
                     // stopnet + stop rule (tacotron2.py:219-224, 257-277), as EPI_MEL_FUSED rule 0;
@@ -1221,6 +1289,7 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
                         a.n_steps[0] = t + 1;
                     }
                     publish_xcd(g1 + PRE, E + 6, nd ? 0.f : 1.f);
+                    if constexpr (!GEN) { RES_EV(t, 11) }
                 }
             }
         }

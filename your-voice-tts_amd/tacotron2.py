@@ -481,9 +481,10 @@ class Tacotron2:
         """Per-CU event trace of the last resident sentence, re-run with event stamps only
         (measurement only): int64 numpy [256 CU, 64 steps, 16 events] of wall-clock ticks (P1, B1,
         h_att published, B3, B4, h_dec published, B6, pre1 row published; synthesis form: partials
-        published, partials gathered, A2, unused; general form: query row published, unused,
-        unused, context published; both: loop-top work done on wave 0 and on wave 3, ahead of the
-        pre1 poll; two unused; 0 = not reached)."""
+        published, partials gathered, A2, continue flag published (stop CUs) | pre1 rows gathered
+        (the others); general form: query row published, unused, unused, context published; both:
+        loop-top work done on wave 0 and on wave 3, ahead of the pre1 poll; synthesis form: next
+        step's attention operands issued, continue flag gathered; 0 = not reached)."""
         lib, hdec, _ = self._handles(1, 1)
         n = 256 * 64 * 16
         buf = (ctypes.c_longlong * n)()
