@@ -19,6 +19,7 @@
 // dot products' issue plus the XCD-local edge, so spreading the rows over more SIMDs pays until
 // the edge dominates.
 #include "encoder_resident.h"
+#include "handoff.h"
 
 #ifndef ENC_SLEEP
 #define ENC_SLEEP 1  // s_sleep between hand-off polls
@@ -27,9 +28,7 @@
 namespace tts {
 namespace {
 
-typedef unsigned long long u64;
-typedef __attribute__((address_space(1))) u64 gu64;
-typedef __attribute__((address_space(1))) int gint;
+using namespace handoff;
 
 #ifndef ENC_RES_WIDE
 #define ENC_RES_WIDE 3
@@ -43,49 +42,6 @@ constexpr int H = 256, G4 = 4 * H;
 constexpr int ER_NW = H / 4 / ER_KS;  // float4 weights per thread
 constexpr int GR_TABLE = 0, GR_H = 256;  // granules: table [256], h [2 parity][2 dir][256]
 
-__device__ __forceinline__ void pub_dev(u64* g, unsigned tag, float v) {
-    __hip_atomic_store((gu64*)g, ((u64)tag << 32) | (u64)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void pub_xcd(u64* g, unsigned tag, float v) {
-    __hip_atomic_store((gu64*)g, ((u64)tag << 32) | (u64)__float_as_uint(v), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ u64 peek(u64* g) {
-    return __hip_atomic_load((gu64*)g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// one wave: lane l polls granules base + 4l .. 4l+3 until every tag matches
-__device__ __forceinline__ bool sweep4(u64* g, unsigned tag, float (&v)[4], long long tmo) {
-    const int lane = threadIdx.x & 63;
-    long long t_end = 0;
-    for (int spin = 0;; ++spin) {
-        bool ok = true;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const u64 x = peek(g + lane * 4 + i);
-            v[i] = __uint_as_float((unsigned)x);
-            ok = ok && (unsigned)(x >> 32) == tag;
-        }
-        if (__all(ok)) return true;
-        if (spin == 0) t_end = (long long)wall_clock64() + tmo;
-        else if ((spin & 31) == 0 && (long long)wall_clock64() > t_end) return false;
-        if (ENC_SLEEP) __builtin_amdgcn_s_sleep(ENC_SLEEP);
-    }
-}
-// one lane polls the 16-byte granule pair `pair` (granules 2 pair, 2 pair + 1 of rsrc r) until
-// both tags match (sc1 | volatile buffer loads: L1 bypass, re-issued every poll)
-typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ bool sweep_pair(__amdgpu_buffer_rsrc_t r, int pair, unsigned tag, float (&v)[2], long long tmo) {
-    long long t_end = 0;
-    for (int spin = 0;; ++spin) {
-        const u32x4_ x = __builtin_bit_cast(u32x4_, __builtin_amdgcn_raw_buffer_load_b128(r, pair * 16, 0, (int)0x80000010u));
-        v[0] = __uint_as_float(x.x);
-        v[1] = __uint_as_float(x.z);
-        if (__all(x.y == tag && x.w == tag)) return true;
-        if (spin == 0) t_end = (long long)wall_clock64() + tmo;
-        else if ((spin & 31) == 0 && (long long)wall_clock64() > t_end) return false;
-        if (ENC_SLEEP) __builtin_amdgcn_s_sleep(ENC_SLEEP);
-    }
-}
 __device__ __forceinline__ float dot4(float4 w, float4 x, float acc) {
     acc = fmaf(w.x, x.x, acc);
     acc = fmaf(w.y, x.y, acc);
@@ -99,32 +55,23 @@ __global__ __launch_bounds__(ER_THREADS, 1) void encoder_resident_kernel(const E
     __shared__ __align__(16) float hsb[2][H];  // h_{s-1} by step parity (the gather fills the other)
     __shared__ int info[4];
     // ---- roles from the XCD table
-    int xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    xcc &= 7;
-    const unsigned setup_tag = (a.salt << 14) | 0x3FFFu;
-    if (tid == 0) pub_dev(a.gran + GR_TABLE + c, setup_tag, __int_as_float(xcc));
+    const int xcc = xcc_id();
+    const XcdCensus cen = xcd_census<0, ENC_SLEEP>(a.gran + GR_TABLE, c, xcc, (a.salt << 14) | 0x3FFFu, a.tmo);
     if (wave == 0) {
-        float v[4];
-        const bool ok = sweep4(a.gran + GR_TABLE, setup_tag, v, a.tmo);
-        const int xref = __builtin_amdgcn_readfirstlane(__float_as_int(v[0]) & 7);
+        const bool ok = cen.ok;
+        const int xref = cen.first_xcd();
         // ER_SPLIT: the backward direction on the XCD of the first workgroup off xref's XCD
         int first = 1 << 20;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const u64 m = __ballot((__float_as_int(v[i]) & 7) != xref);
+            const u64 m = __ballot(cen.raw[i] != xref);
             if (m) first = min(first, 4 * __builtin_ctzll(m) + i);
         }
-        const int xref1 = ER_SPLIT && first < 256 ? __float_as_int(__uint_as_float((unsigned)peek(a.gran + GR_TABLE + first))) & 7 : xref;
-        const int xmine = ER_SPLIT && xcc == xref1 ? xref1 : xref;
-        int rank = 0, nref = 0, nref1 = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int x = __float_as_int(v[i]) & 7;
-            nref += __popcll(__ballot(x == xref));
-            nref1 += __popcll(__ballot(x == xref1));
-            rank += __popcll(__ballot(x == xmine && lane * 4 + i < c));
-        }
+        const int xref1 = ER_SPLIT && first < 256 ? (int)peek(a.gran + GR_TABLE + first) & 7 : xref;
+        // (a workgroup on neither XCD takes no role, whatever its rank)
+        const int rank = cen.rank;
+        int nref = cen.count(xref);
+        const int nref1 = cen.count(xref1);
         if (ER_SPLIT) {
             if (xref1 == xref) nref = 0;  // one XCD only: no placement for the split form
             nref = min(nref, nref1) * 2;  // the roles need ER_SLOTS on each of the two XCDs
@@ -137,10 +84,8 @@ __global__ __launch_bounds__(ER_THREADS, 1) void encoder_resident_kernel(const E
             info[2] = nref;
             info[3] = 0;
             // status word = salt << 8 | code (res_status_code): no clearing between launches
-            if (!ok) __hip_atomic_store((gint*)a.status, (int)((a.salt << 8) | 6u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else if (nref < 2 * ER_SLOTS && c == 0)
-                __hip_atomic_store((gint*)a.status, (int)((a.salt << 8) | (unsigned)ENC_RES_STATUS_PLACEMENT), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
+            if (!ok) fail_word(a.status, (int)((a.salt << 8) | 6u));
+            else if (nref < 2 * ER_SLOTS && c == 0) fail_word(a.status, (int)((a.salt << 8) | (unsigned)ENC_RES_STATUS_PLACEMENT));
         }
     }
     __syncthreads();
@@ -199,21 +144,30 @@ __global__ __launch_bounds__(ER_THREADS, 1) void encoder_resident_kernel(const E
             cs = f * cs + act * g;  // c' = s(f) c + s(i) tanh(g)
             const float h = o * tanh_cell(cs);
             hlast = h;
-            pub_xcd(gh + unit, (a.salt << 14) | (unsigned)(s + 1), h);
+            publish_xcd(gh + unit, (a.salt << 14) | (unsigned)(s + 1), h);
             const int pos = dir == 0 ? s : L - 1 - s;
             a.out[(int64_t)pos * (2 * H) + dir * H + unit] = h;
         }
         xcur = xnext;
         if (wave < 2) {
             // the direction's 256 h values: one 16-byte granule pair per lane on waves 0 and 1
-            // (one load instruction per poll instead of four on one wave)
+            // (one load instruction per poll instead of four on one wave: sc1 | volatile buffer
+            // loads, L1 bypass, re-issued every poll; no empty lanes)
             float v[2];
             const int pr = wave * 64 + lane;
-            for (int i = 0; i < a.first_sleep; ++i) __builtin_amdgcn_s_sleep(1);
-            const bool ok = sweep_pair(gr, ((par * 2 + dir) * H) / 2 + pr, (a.salt << 14) | (unsigned)(s + 1), v, a.tmo);
+            const int pair = ((par * 2 + dir) * H) / 2 + pr;
+            const unsigned tag = (a.salt << 14) | (unsigned)(s + 1);
+            first_poll_delay<1>(a.first_sleep);
+            const bool ok = poll_until<0, ENC_SLEEP>(
+                [&] {
+                    const u32x4 x = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(gr, pair * 16, 0, SC1_VOLATILE));
+                    v[0] = __uint_as_float(x.x);
+                    v[1] = __uint_as_float(x.z);
+                    return x.y == tag && x.w == tag;
+                },
+                a.tmo);
             if (!ok) {
-                if (lane == 0)
-                    __hip_atomic_store((gint*)a.status, (int)((a.salt << 8) | 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (lane == 0) fail_word(a.status, (int)((a.salt << 8) | 1u));
                 info[3] = 1;
             }
             *reinterpret_cast<float2*>(hsb[(s + 1) & 1] + pr * 2) = float2{v[0], v[1]};
@@ -246,34 +200,18 @@ __global__ __launch_bounds__(EB_THREADS, 1) void encoder_resident_batch_kernel(c
     __shared__ __align__(16) float hs[2][EB_G][EB_LDH];  // h_{s-1} of the group's sentences, by parity
     __shared__ __align__(16) float red[8][64][4];        // partial gate tiles
     __shared__ int info[4];
-    int xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    xcc &= 7;
-    const unsigned setup_tag = (a.salt << 14) | 0x3FFFu;
-    if (tid == 0) pub_dev(a.gran + EB_GR_TABLE + c, setup_tag, __int_as_float(xcc));
+    const int xcc = xcc_id();
+    const XcdCensus cen = xcd_census<0, ENC_SLEEP>(a.gran + EB_GR_TABLE, c, xcc, (a.salt << 14) | 0x3FFFu, a.tmo);
     if (wave == 0) {
-        float v[4];
-        const bool ok = sweep4(a.gran + EB_GR_TABLE, setup_tag, v, a.tmo);
-        int rank = 0, nmin = 256;
-        for (int x = 0; x < 8; ++x) {
-            int cnt = 0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int xi = __float_as_int(v[i]) & 7;
-                cnt += __popcll(__ballot(xi == x));
-                if (x == xcc) rank += __popcll(__ballot(xi == x && lane * 4 + i < c));
-            }
-            nmin = min(nmin, cnt);
-        }
+        int nmin = 256;  // (an XCD without a workgroup counts: every XCD has a role)
+        for (int x = 0; x < 8; ++x) nmin = min(nmin, cen.count(x));
         if (lane == 0) {
-            info[0] = ok ? 1 : 0;
-            info[1] = rank;
+            info[0] = cen.ok ? 1 : 0;
+            info[1] = cen.rank;
             info[2] = nmin;
             info[3] = 0;
-            if (!ok) __hip_atomic_store((gint*)a.status, (int)((a.salt << 8) | 6u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else if (nmin < 32 && c == 0)
-                __hip_atomic_store((gint*)a.status, (int)((a.salt << 8) | (unsigned)ENC_RES_STATUS_PLACEMENT), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
+            if (!cen.ok) fail_word(a.status, (int)((a.salt << 8) | 6u));
+            else if (nmin < 32 && c == 0) fail_word(a.status, (int)((a.salt << 8) | (unsigned)ENC_RES_STATUS_PLACEMENT));
         }
     }
     __syncthreads();
@@ -336,39 +274,35 @@ __global__ __launch_bounds__(EB_THREADS, 1) void encoder_resident_batch_kernel(c
                 a.out[((int64_t)bsen * a.Tmax + pos) * (2 * H) + dir * H + unit] = h;
             }
             // every lane publishes (idle sentences: their last h) so the gather sees every tag
-            pub_xcd(gx + (int64_t)(par * 8 + xcc) * EB_GR_PER + n * H + unit, (a.salt << 14) | (unsigned)(s + 1), hprev);
+            publish_xcd(gx + (int64_t)(par * 8 + xcc) * EB_GR_PER + n * H + unit, (a.salt << 14) | (unsigned)(s + 1), hprev);
         }
         // ---- gather the group's h_s into the other buffer: thread t sweeps granules t + 512 i
         {
             const unsigned tag = (a.salt << 14) | (unsigned)(s + 1);
             u64* gp = gx + (int64_t)(par * 8 + xcc) * EB_GR_PER;
-            long long t_end = 0;
             constexpr int PER = EB_GR_PER / EB_THREADS;  // 8
             float v[PER];
-            bool ok = true;
-            for (int spin = 0;; ++spin) {
-                ok = true;
+            const bool ok = poll_until<0, ENC_SLEEP>(
+                [&] {
+                    bool ok = true;
 #pragma unroll
-                for (int i = 0; i < PER; ++i) {
-                    const int gidx = tid + i * EB_THREADS, nn = gidx / H;
-                    if (nn < nb) {
-                        const u64 x = peek(gp + gidx);
-                        v[i] = __uint_as_float((unsigned)x);
-                        ok = ok && (unsigned)(x >> 32) == tag;
-                    } else {
-                        v[i] = 0.f;
+                    for (int i = 0; i < PER; ++i) {
+                        const int gidx = tid + i * EB_THREADS, nn = gidx / H;
+                        if (nn < nb) {
+                            const u64 x = peek(gp + gidx);
+                            v[i] = __uint_as_float((unsigned)x);
+                            ok = ok && (unsigned)(x >> 32) == tag;
+                        } else {
+                            v[i] = 0.f;
+                        }
                     }
-                }
-                if (__all(ok)) break;
-                if (spin == 0) t_end = (long long)wall_clock64() + a.tmo;
-                else if ((spin & 31) == 0 && (long long)wall_clock64() > t_end) break;
-                if (ENC_SLEEP) __builtin_amdgcn_s_sleep(ENC_SLEEP);
-            }
-            if (!__all(ok)) {
-                if (lane == 0) {
-                    __hip_atomic_store((gint*)a.status, (int)((a.salt << 8) | 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    info[3] = 1;
-                }
+                    return ok;
+                },
+                a.tmo);
+            // (a timed-out gather still writes what it read: the workgroup leaves below)
+            if (!ok && lane == 0) {
+                fail_word(a.status, (int)((a.salt << 8) | 1u));
+                info[3] = 1;
             }
 #pragma unroll
             for (int i = 0; i < PER; ++i) {

@@ -32,12 +32,14 @@
 #include <vector>
 
 #include "gl_fft.h"
+#include "handoff.h"
 
 #ifndef GLP_SLEEP
 #define GLP_SLEEP 1  // persistent loop: s_sleep between neighbour-tag polls
 #endif
 
 using namespace tts;
+using namespace tts::handoff;
 
 namespace {
 
@@ -784,8 +786,6 @@ __device__ __forceinline__ double2 inv_presplit2(double2 xk, double2 xm, double2
 }
 
 // buffer-resource access (SGPR base + 32-bit lane offset; out-of-range loads read 0, stores drop)
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* p, unsigned bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
 }
@@ -1067,17 +1067,12 @@ struct PersArgs {
     int drop_f;         // fault injection (tests, TTS_GL_INJECT_DROP): sentence 0's frame drop_f stops
                         // after its first iteration without storing it (-1: none)
 };
-constexpr int GL_SC1_VOLATILE = (int)0x80000010u;  // buffer aux: sc1 (bit 4) | volatile (bit 31)
-constexpr int GL_OOB_OFF = 0x7FFFFFF0;               // past every granule buffer: reads 0, no access
 constexpr int GL_DMAX = 4;                            // overlap-add contributors lie within 4 frames
 constexpr int GL_SLOTS = 2 * GL_DMAX + 1;              // gather buffer slots (frames f-4 .. f+4)
 constexpr int GL_PAIRS = 9;                            // granule pairs per thread (<= 2304 per frame:
                                                        // 2216 at most for n_fft 2048 / win 1102 / hop 275)
 // fill word of a fresh (or salt-wrapped) granule buffer, every dword: tag 1 = salt 0, never a live tag
 constexpr unsigned GL_GRAN_FILL = 1u;
-typedef __attribute__((address_space(1))) unsigned long long gu64_t;
-typedef __attribute__((address_space(1))) unsigned gu32_t;
-typedef __attribute__((address_space(1))) int gi32_t;
 
 // TWO: the form for 257..512 frames, two workgroups per compute unit (one wave per SIMD each):
 // at most 256 registers per lane (the FFT twiddles read pass by pass, fft1024_regs_gtw, instead of
@@ -1095,38 +1090,30 @@ __device__ __forceinline__ void gl_persistent_body(const PersArgs& p) {
     __shared__ __align__(16) double2 buf1[NH];  // Z, then the inverse wave regions
     __shared__ int sh[4];  // frame, local stores, abort
     auto fail = [&](int code) {
-        __hip_atomic_store((gi32_t*)p.status, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        fail_word(p.status, code);
         sh[2] = 1;
     };
     if (tid == 0) sh[2] = 0;
     // ---- placement: frames -> XCDs in contiguous runs over where the workgroups actually run
-    int xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    xcc &= 7;
+    const int xcc = xcc_id();
     unsigned* xt = p.xtab + (int64_t)b * a.Fmax;
-    if (tid == 0)
-        __hip_atomic_store((gu32_t*)(xt + blockIdx.x), (p.salt << 8) | (unsigned)xcc, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) publish32_agent(xt + blockIdx.x, (p.salt << 8) | (unsigned)xcc);
     constexpr int PV = TWO ? 8 : 4;  // table entries per lane (Fb <= 64 PV)
     if (wave == 0) {
         unsigned v[PV];  // blocks PV lane .. PV lane + PV - 1
-        long long t_end = 0;
-        bool ok = true;
-        for (int spin = 0;; ++spin) {
-            ok = true;
+        // (a timed-out table still yields ranks below; the launch then fails with code 2)
+        const bool ok = poll_until<0, 0>(
+            [&] {
+                bool ok = true;
 #pragma unroll
-            for (int i = 0; i < PV; ++i) {
-                const int k = lane * PV + i;
-                v[i] = k < Fb ? __hip_atomic_load((gu32_t*)(xt + k), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-                ok = ok && (k >= Fb || (v[i] >> 8) == p.salt);
-            }
-            if (__all(ok)) break;
-            if (spin == 0) {
-                t_end = (long long)wall_clock64() + p.tmo;
-            } else if ((spin & 31) == 0 && (long long)wall_clock64() > t_end) {
-                break;
-            }
-        }
+                for (int i = 0; i < PV; ++i) {
+                    const int k = lane * PV + i;
+                    v[i] = k < Fb ? peek32(xt + k) : 0u;
+                    ok = ok && (k >= Fb || (v[i] >> 8) == p.salt);
+                }
+                return ok;
+            },
+            p.tmo);
         int base = 0, cnt = 0, rank = 0;
         for (int x = 0; x < 8; ++x) {
             int c = 0, r = 0;
@@ -1144,7 +1131,7 @@ __device__ __forceinline__ void gl_persistent_body(const PersArgs& p) {
             const int f = base + rank;
             sh[0] = f;
             sh[1] = f - 4 >= base && f + 4 < base + cnt && f >= 5 && f <= Fb - 6;
-            if (!__all(ok)) fail(2);
+            if (!ok) fail(2);
         }
     }
     __syncthreads();
@@ -1256,14 +1243,14 @@ __device__ __forceinline__ void gl_persistent_body(const PersArgs& p) {
     }
     const int gbase = (f - GL_DMAX) * g.winp * 8;
     auto goff = [&](int m) {
-        return (gdst[m] >> 30) ? gbase + (int)(gdst[m] & 0x3FFFFFFFu) * 8 : GL_OOB_OFF;
+        return (gdst[m] >> 30) ? gbase + (int)(gdst[m] & 0x3FFFFFFFu) * 8 : OOB_OFF;
     };
     // byte offset of output sample i's granule in the frame slot (computed where stored); samples
     // outside the window support take an out-of-range offset (the buffer store drops them)
     // (TWO: computed where stored, from an opaque thread index: held, they would not fit)
     auto soff_of = [&](int t, int i) {
         const int e = edge_sample(t, i);
-        return (unsigned)(e - g.woff) < (unsigned)g.win ? (e - g.fb) * 8 : GL_OOB_OFF;
+        return (unsigned)(e - g.woff) < (unsigned)g.win ? (e - g.fb) * 8 : OOB_OFF;
     };
     int soffv[TWO ? 1 : PN];
     if constexpr (!TWO) {
@@ -1295,27 +1282,21 @@ __device__ __forceinline__ void gl_persistent_body(const PersArgs& p) {
         // flight at once), re-read until every needed tag is this iteration's, then into LDS
         {
             const auto rG = buf_rsrc(src, (unsigned)(a.Fmax * g.winp * 8));
-            long long t_end = 0;
             u32x4 x[GL_PAIRS];
-            // (a poll storm from every workgroup the moment it has stored slows the stores it waits for)
-            for (int i = 0; i < p.first_sleep; ++i) __builtin_amdgcn_s_sleep(4);
-            for (int spin = 0;; ++spin) {
+            first_poll_delay<4>(p.first_sleep);
+            const bool ok = poll_until<0, GLP_SLEEP>(
+                [&] {
 #pragma unroll
-                for (int m = 0; m < GL_PAIRS; ++m)
-                    x[m] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rG, goff(m), 0, GL_SC1_VOLATILE));
-                bool ok = true;
+                    for (int m = 0; m < GL_PAIRS; ++m)
+                        x[m] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rG, goff(m), 0, SC1_VOLATILE));
+                    bool ok = true;
 #pragma unroll
-                for (int m = 0; m < GL_PAIRS; ++m)
-                    ok = ok && (!(gdst[m] & (1u << 30)) || x[m].y == want) && (!(gdst[m] & (1u << 31)) || x[m].w == want);
-                if (__all(ok) || p.nowait) break;
-                if (spin == 0) {
-                    t_end = (long long)wall_clock64() + p.tmo;
-                } else if ((spin & 31) == 0 && (long long)wall_clock64() > t_end) {
-                    if (lane == 0) fail(1);
-                    break;
-                }
-                if (GLP_SLEEP) __builtin_amdgcn_s_sleep(GLP_SLEEP);
-            }
+                    for (int m = 0; m < GL_PAIRS; ++m)
+                        ok = ok && (!(gdst[m] & (1u << 30)) || x[m].y == want) && (!(gdst[m] & (1u << 31)) || x[m].w == want);
+                    return ok || p.nowait;  // (nowait: leaves after one sweep)
+                },
+                p.tmo);
+            if (!ok && lane == 0) fail(1);
             // (unneeded granules of a pair land on LDS words no sum reads; out-of-range pairs write
             // zeros to the zero word)
 #pragma unroll
@@ -1361,7 +1342,7 @@ __device__ __forceinline__ void gl_persistent_body(const PersArgs& p) {
             const u32x4 gv = u32x4{__float_as_uint((float)(wi[2 * r] * (v[r].x * (1.0 / NH)))), nt,
                                    __float_as_uint((float)(wi[2 * r + 1] * (v[r].y * (1.0 / NH)))), nt};
             const int e = edge_sample(TWO ? tid_opaque() : tid, 2 * r);
-            const int off = e + 1 >= g.woff && e < g.woff + g.win ? (e - g.fb) * 8 : GL_OOB_OFF;
+            const int off = e + 1 >= g.woff && e < g.woff + g.win ? (e - g.fb) * 8 : OOB_OFF;
             // plain (workgroup-scope) store: the line stays in this XCD's L2; sc1: written through
             if (local) __builtin_amdgcn_raw_buffer_store_b128(gv, rD, off, 0, 0);
             else __builtin_amdgcn_raw_buffer_store_b128(gv, rD, off, 0, 0x10);

@@ -156,42 +156,6 @@ __device__ __forceinline__ float dot4(float4 w, float4 x, float acc) {
     acc = fmaf(w.z, x.z, acc);
     return fmaf(w.w, x.w, acc);
 }
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-
-// Poll NP consecutive granule pairs from even slot `base` (thread i: pairs i, i + 256, ...): every
-// poll issues all of the thread's loads before one wait; the values go to dst[2p], dst[2p + 1]
-// once every pair of the wave carries `tag`.  false after the timeout.
-template <int NP>
-__device__ __forceinline__ bool gather_pairs(__amdgpu_buffer_rsrc_t r, int base, unsigned tag, float* dst, long long tmo,
-                                             int first_sleep = 0) {
-    static_assert(NP % RB_THREADS == 0, "whole pairs per thread");
-    constexpr int MAXP = NP / RB_THREADS;
-    const int tid = threadIdx.x;
-    long long t_end = 0;
-    // (a poll storm from every CU the moment it has published slows the stores it waits for)
-    for (int i = 0; i < first_sleep; ++i) __builtin_amdgcn_s_sleep(4);
-    for (int spin = 0;; ++spin) {
-        u32x4 x[MAXP];
-#pragma unroll
-        for (int i = 0; i < MAXP; ++i)
-            x[i] = __builtin_bit_cast(
-                u32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (base + 2 * (tid + i * RB_THREADS)) * 8, 0, SC1_VOLATILE));
-        bool ok = true;
-#pragma unroll
-        for (int i = 0; i < MAXP; ++i) ok = ok && x[i].y == tag && x[i].w == tag;
-        if (__all(ok)) {
-#pragma unroll
-            for (int i = 0; i < MAXP; ++i)
-                *reinterpret_cast<float2*>(dst + 2 * (tid + i * RB_THREADS)) = float2{__uint_as_float(x[i].x), __uint_as_float(x[i].z)};
-            return true;
-        }
-        if (spin == 0) {
-            t_end = (long long)wall_clock64() + tmo;
-        } else if ((spin & 31) == 0 && (long long)wall_clock64() > t_end) {
-            return false;
-        }
-    }
-}
 
 // GEN: the general attention form (location features, windowing, transition agent); the other
 // instantiations carry none of its code.
@@ -287,11 +251,9 @@ __global__ __launch_bounds__(RB_THREADS, 1) void resident_batch_kernel(const Res
     __syncthreads();
     const long long tmo = a.timeout_ticks;
     // ---- XCD discovery (as the batch-1 kernel): exactly 32 workgroups per XCD
-    int xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    xcc &= 7;
+    const int xcc = xcc_id();
     const unsigned setup_tag = (a.salt << 14) | 0x3FFFu;
-    if (tid == 0) publish(a.gran + RBG_SETUP + c, setup_tag, __int_as_float(xcc));
+    if (tid == 0) publish_agent(a.gran + RBG_SETUP + c, setup_tag, __int_as_float(xcc));
     if (wave == 0) {
         float v4[4];
         const bool ok = sweep<4>(a.gran, setup_tag, v4, [&](int i) { return RBG_SETUP + lane * 4 + i; }, tmo);
@@ -487,7 +449,7 @@ __global__ __launch_bounds__(RB_THREADS, 1) void resident_batch_kernel(const Res
         if (t == 0) {
             for (int k = tid; k < NB * PRE; k += RB_THREADS) xp1[k] = k < a.B * PRE ? a.pre1[k] : 0.f;
         } else {
-            const bool ok = gather_pairs<NB * PRE / 2>(rg, Pp + xb + RBX_P1, EP6, xp1, tmo);
+            const bool ok = gather_pairs<NB * PRE / 2, RB_THREADS>(rg, Pp + xb + RBX_P1, EP6, xp1, tmo);
             if (!ok && lane == 0) { flags[1] = 1; fail(a.status, 1, t); }
             if (wave == 0) {
                 float f0 = 0.f, f1 = 0.f;
@@ -527,7 +489,7 @@ __global__ __launch_bounds__(RB_THREADS, 1) void resident_batch_kernel(const Res
         }
         mark(2);
         {
-            const bool ok = gather_pairs<NB * PRE / 2>(rg, P + xb + RBX_PRE2, E + 1, xpre, tmo, a.sleep_pre2);
+            const bool ok = gather_pairs<NB * PRE / 2, RB_THREADS>(rg, P + xb + RBX_PRE2, E + 1, xpre, tmo, a.sleep_pre2);
             if (!ok && lane == 0) { flags[1] = 1; fail(a.status, 7, t); }
         }
         __syncthreads();  // P2
@@ -547,7 +509,7 @@ __global__ __launch_bounds__(RB_THREADS, 1) void resident_batch_kernel(const Res
                 const float gg = tanh_cell(z.z + bia[2]), og = sigmoid_cell(z.w + bia[3]);
                 c_att = fg * c_att + ig * gg;
                 h_att_l = og * tanh_cell(c_att);
-                publish(G + RBG_HATT + lane * HATT + 4 * c + wave, E + 2, h_att_l);
+                publish_agent(G + RBG_HATT + lane * HATT + 4 * c + wave, E + 2, h_att_l);
             }
         }
         // the decoder LSTM's h_dec_{t-1} half now: useful work before the first h_att poll (a poll
@@ -566,7 +528,7 @@ __global__ __launch_bounds__(RB_THREADS, 1) void resident_batch_kernel(const Res
         mark(4);
         // 5) gather h_att_t
         {
-            const bool ok = gather_pairs<NB * HATT / 2>(rg, P + RBG_HATT, E + 2, xh_att, tmo, a.sleep_hatt);
+            const bool ok = gather_pairs<NB * HATT / 2, RB_THREADS>(rg, P + RBG_HATT, E + 2, xh_att, tmo, a.sleep_hatt);
             if (!ok && lane == 0) { flags[1] = 1; fail(a.status, 2, t); }
         }
         __syncthreads();  // P3
@@ -761,7 +723,7 @@ __global__ __launch_bounds__(RB_THREADS, 1) void resident_batch_kernel(const Res
         mark(8);
         // 9) gather the NB contexts and tails
         {
-            const bool ok = gather_pairs<NB * ENC / 2>(rg, P + xb + RBX_CTX, E + 4, xctx, tmo, a.sleep_ctx);
+            const bool ok = gather_pairs<NB * ENC / 2, RB_THREADS>(rg, P + xb + RBX_CTX, E + 4, xctx, tmo, a.sleep_ctx);
             if (!ok && lane == 0) { flags[1] = 1; fail(a.status, 4, t); }
             if (wave == 1) {
                 float t0 = 0.f, t1 = 0.f;
@@ -795,7 +757,7 @@ __global__ __launch_bounds__(RB_THREADS, 1) void resident_batch_kernel(const Res
                 const float gg = tanh_cell(z.z + bid[2]), og = sigmoid_cell(z.w + bid[3]);
                 c_dec = fg * c_dec + ig * gg;
                 h_dec_l = og * tanh_cell(c_dec);
-                publish(G + RBG_HDEC + lane * HDEC + 4 * c + wave, E + 5, h_dec_l);
+                publish_agent(G + RBG_HDEC + lane * HDEC + 4 * c + wave, E + 5, h_dec_l);
             }
         }
         mark(10);
@@ -837,7 +799,7 @@ __global__ __launch_bounds__(RB_THREADS, 1) void resident_batch_kernel(const Res
             w1p[6 + i] = ld4(w1a + KF + i * 256);
         }
         {
-            const bool ok = gather_pairs<NB * HDEC / 2>(rg, P + RBG_HDEC, E + 5, xh_dec, tmo, a.sleep_hdec);
+            const bool ok = gather_pairs<NB * HDEC / 2, RB_THREADS>(rg, P + RBG_HDEC, E + 5, xh_dec, tmo, a.sleep_hdec);
             if (!ok && lane == 0) { flags[1] = 1; fail(a.status, 5, t); }
         }
         __syncthreads();  // P5

@@ -63,7 +63,6 @@ __device__ __forceinline__ float dot4(float4 w, float4 x, float acc) {
     acc = fmaf(w.z, x.z, acc);
     return fmaf(w.w, x.w, acc);
 }
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 // Keeps four loaded float4 live at one point: the loads that fill them all issue before it
 __device__ __forceinline__ void pin4(float4& a, float4& b, float4& c, float4& d) {
     asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w), "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.w), "+v"(c.x),
@@ -309,11 +308,9 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
     // ---- XCD discovery: prenet-2 is computed and exchanged inside each XCD (same-L2 hand-off).
     // Every CU publishes its XCC id; each reads the table, takes rank = #CUs of its XCD before it,
     // and computes rows [rank * 256 / n, (rank + 1) * 256 / n) of its XCD's copy of prenet-2.
-    int xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    xcc &= 7;
+    const int xcc = xcc_id();
     const unsigned setup_tag = (a.salt << 14) | 0x3FFFu;
-    if (tid == 0) publish(a.gran + GR_SETUP + c, setup_tag, __int_as_float(xcc));
+    if (tid == 0) publish_agent(a.gran + GR_SETUP + c, setup_tag, __int_as_float(xcc));
     if (wave == 0) {
         float v4[4];
         // (synthesis form: the strict bound.  Its step waits all follow useful work and none spins
@@ -662,7 +659,7 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
             if (tid < 4) {
                 st[32 + tid] = cs;
                 st[40 + tid] = h;
-                publish(G + GR_HATT + 4 * c + tid, E + 2, h);
+                publish_agent(G + GR_HATT + 4 * c + tid, E + 2, h);
                 if (tid == 0) { RES_EV(t, 2) }
             }
         }
@@ -1124,7 +1121,7 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
             if (tid < 4) {
                 st[36 + tid] = cs;
                 st[44 + tid] = h;
-                publish(G + GR_HDEC + 4 * c + tid, E + 5, h);
+                publish_agent(G + GR_HDEC + 4 * c + tid, E + 5, h);
                 if (tid == 0) { RES_EV(t, 5) }
             }
         }

@@ -23,14 +23,21 @@
 // reference (alignment = sig / sum sig) cancels in it, so it is not reduced (same values up to
 // float32 rounding).  Every other reduction follows a fixed order (bitwise run-to-run
 // deterministic).  Every wait is bounded; a timed-out wait flags the status and drains the grid.
+#include "handoff.h"
 #include "tacotron.h"
 
 namespace tts {
 namespace {
 
-typedef unsigned long long u64;
-typedef __attribute__((address_space(1))) u64 gu64;
-typedef __attribute__((address_space(1))) int gint;
+using namespace handoff;
+
+// every step wait of this kernel: the clock compared on spins 1, 33, ..., no s_sleep between polls,
+// first_sleep x s_sleep(1) ahead of the first poll
+constexpr int TR_CHECK_AT = 1, TR_SLEEP = 0, TR_FIRST_SLEEP_T = 1;
+template <int N, typename F>
+__device__ __forceinline__ bool tr_sweep(u64* g, unsigned tag, float (&v)[N], F idx, long long tmo, int first_sleep = 0) {
+    return sweep_flat<N, TR_CHECK_AT, TR_SLEEP, TR_FIRST_SLEEP_T>(g, tag, v, idx, tmo, first_sleep);
+}
 
 constexpr int TD = T_DEC;                    // 256
 constexpr int ADIM = 128;                    // attention_dim
@@ -80,50 +87,6 @@ constexpr int L_WM = L_W1 + TR_WAVES * 8 * 64;           // [8 waves][8][64] pro
 constexpr int L_PROF = L_WM + TR_WAVES * 8 * 64;          // [TR_PHASES] u64 phase timers (measurement)
 constexpr int L_TOTAL = L_PROF + 2 * TR_PHASES;
 
-__device__ __forceinline__ void publish(u64* g, unsigned tag, float v) {
-    __hip_atomic_store((gu64*)g, ((u64)tag << 32) | (u64)__float_as_uint(v), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void publish_agent(u64* g, unsigned tag, float v) {
-    __hip_atomic_store((gu64*)g, ((u64)tag << 32) | (u64)__float_as_uint(v), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ u64 peek(u64* g) {
-    return __hip_atomic_load((gu64*)g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void fail(int* status, int code) {
-    __hip_atomic_store((gint*)status, code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// One wave polls its N granules per lane (idx(i) < 0: none) until every tag equals `tag`; false
-// after `tmo` wall-clock ticks.
-template <int N, typename F>
-__device__ __forceinline__ bool sweep(u64* g, unsigned tag, float (&v)[N], F idx, long long tmo, int first_sleep = 0) {
-    long long t_end = 0;
-    // (a poll storm from every CU of the XCD the moment it has published slows the stores it waits for)
-    for (int i = 0; i < first_sleep; ++i) __builtin_amdgcn_s_sleep(1);
-    for (int spin = 0;; ++spin) {
-        bool ok = true;
-        // every load issued unconditionally (a slot with idx < 0 re-reads slot 0 and is ignored), so
-        // the N loads of a poll are in flight together
-        u64 x[N];
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            const int k = idx(i);
-            x[i] = peek(g + (k >= 0 ? k : 0));
-        }
-#pragma unroll
-        for (int i = 0; i < N; ++i) {
-            v[i] = __uint_as_float((unsigned)x[i]);
-            ok = ok & ((idx(i) < 0) | ((unsigned)(x[i] >> 32) == tag));  // no short-circuit branches
-        }
-        if (__all(ok)) return true;
-        if (spin == 0) {
-            t_end = (long long)wall_clock64() + tmo;
-        } else if ((spin & 31) == 1 && (long long)wall_clock64() > t_end) {
-            return false;
-        }
-    }
-}
 // sum over the 16 lanes of each DPP row: the total lands in lane 15 of the row
 __device__ __forceinline__ float row_sum16(float v) {
     v += dpp_move<0x111, 0xf>(v, 0.f);
@@ -132,8 +95,6 @@ __device__ __forceinline__ float row_sum16(float v) {
     v += dpp_move<0x118, 0xf>(v, 0.f);
     return v;
 }
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ float2 ld2(const float* p) { return *reinterpret_cast<const float2*>(p); }
 template <int CTRL>
 __device__ __forceinline__ float dpp_all(float v) {  // full-wave DPP move, every lane written
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
@@ -212,32 +173,21 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
         plast = now_;                                           \
     }
     // ---- XCD discovery: rank = #CUs of this XCD with a lower block index
-    int xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    xcc &= 7;
-    const unsigned setup_tag = (a.salt << 14) | 0x3FFFu;
-    if (tid == 0) publish_agent(a.gran + G_SETUP + c, setup_tag, __int_as_float(xcc));
+    const int xcc = xcc_id();
     if (tid == 0) ctl[0] = 0;
+    const XcdCensus cs = xcd_census<TR_CHECK_AT, TR_SLEEP>(a.gran + G_SETUP, c, xcc, (a.salt << 14) | 0x3FFFu, tmo);
     if (wave == 0) {
-        float v4[4];
-        const bool ok = sweep<4>(a.gran + G_SETUP, setup_tag, v4, [&](int i) { return lane * 4 + i; }, tmo);
-        int rank = 0, nx = 0, nmin = TR_CUS;
+        int nmin = TR_CUS;
+        const int nx = cs.count(xcc);
         for (int k = 0; k < 8; ++k) {
-            int cnt = 0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int x = __float_as_int(v4[i]) & 7;
-                cnt += __popcll(__ballot(x == k));
-                if (k == xcc) rank += __popcll(__ballot(x == k && lane * 4 + i < c));
-            }
-            if (k == xcc) nx = cnt;
+            const int cnt = cs.count(k);
             if (cnt > 0) nmin = min(nmin, cnt);
         }
         if (lane == 0) {
-            ctl[1] = rank;
+            ctl[1] = cs.rank;
             ctl[2] = nx;
-            if (!ok) { ctl[0] = 1; fail(a.status, 9); }
-            else if (nmin < TR_RANKS) { ctl[0] = 1; fail(a.status, TR_STATUS_PLACEMENT); }
+            if (!cs.ok) { ctl[0] = 1; fail_word(a.status, 9); }
+            else if (nmin < TR_RANKS) { ctl[0] = 1; fail_word(a.status, TR_STATUS_PLACEMENT); }
         }
     }
     __syncthreads();
@@ -405,14 +355,14 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
         if (t > 0) {
             if (gon) {
                 float v3[3];
-                const bool ok = sweep<3>(Gp + G_PRE1, Ep + P_PRE1, v3, [&](int i) {
+                const bool ok = tr_sweep<3>(Gp + G_PRE1, Ep + P_PRE1, v3, [&](int i) {
                     if (i < 2) return gs * T_PRE1 + gf * 128 + ln + 64 * i;
                     return (wave == 0 && ln < ns) ? TR_SPX * T_PRE1 + ln : -1;
                 }, tmo, fsl);
                 pre1[gs * T_PRE1 + gf * 128 + lane] = v3[0];
                 pre1[gs * T_PRE1 + gf * 128 + 64 + lane] = v3[1];
                 if (wave == 0 && lane < ns) dn[lane] = v3[2] == 0.f ? 1 : 0;
-                if (!ok && lane == 0) { ctl[0] = 1; fail(a.status, 1); }
+                if (!ok && lane == 0) { ctl[0] = 1; fail_word(a.status, 1); }
             }
             __syncthreads();
             if (ctl[0]) return;
@@ -426,13 +376,13 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
             float p[TR_SPX];
             dot4(p, w2q, pre1, T_PRE1, lane);
             const float v = to_lanes(p, lane);
-            if (lane < ns) publish(G + G_PRE2 + lane * T_PRE2 + r2, E + P_PRE2, fmaxf(v + bias[14], 0.f));
+            if (lane < ns) publish_xcd(G + G_PRE2 + lane * T_PRE2 + r2, E + P_PRE2, fmaxf(v + bias[14], 0.f));
         }
         if (gon) {
             float v1[1];
-            const bool ok = sweep<1>(G + G_PRE2, E + P_PRE2, v1, [&](int i) { return gs * T_PRE2 + gf * 64 + ln; }, tmo, fsl);
+            const bool ok = tr_sweep<1>(G + G_PRE2, E + P_PRE2, v1, [&](int i) { return gs * T_PRE2 + gf * 64 + ln; }, tmo, fsl);
             xa[gs * TXA + gf * 64 + lane] = v1[0];
-            if (!ok && lane == 0) { ctl[0] = 1; fail(a.status, 2); }
+            if (!ok && lane == 0) { ctl[0] = 1; fail_word(a.status, 2); }
         }
         __syncthreads();
         if (ctl[0]) return;
@@ -473,16 +423,16 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
                 const float rg = sigmoid_cell(R + bias[0]);
                 const float zg = sigmoid_cell(Z + bias[1]);
                 const float ng = tanh_cell((N + bias[2]) + rg * (Q + bias[3]));
-                publish(G + G_HATT + lane * TD + U, E + P_HATT, (hatt_prev[lane * TD + U] - ng) * zg + ng);
+                publish_xcd(G + G_HATT + lane * TD + U, E + P_HATT, (hatt_prev[lane * TD + U] - ng) * zg + ng);
             }
         }
         MARK(12);
         if (gon) {
             float v2[2];
-            const bool ok = sweep<2>(G + G_HATT, E + P_HATT, v2, [&](int i) { return gs * TD + gf * 128 + ln + 64 * i; }, tmo, fsl);
+            const bool ok = tr_sweep<2>(G + G_HATT, E + P_HATT, v2, [&](int i) { return gs * TD + gf * 128 + ln + 64 * i; }, tmo, fsl);
             hatt[gs * TD + gf * 128 + lane] = v2[0];
             hatt[gs * TD + gf * 128 + 64 + lane] = v2[1];
-            if (!ok && lane == 0) { ctl[0] = 1; fail(a.status, 3); }
+            if (!ok && lane == 0) { ctl[0] = 1; fail_word(a.status, 3); }
         }
         __syncthreads();
         if (ctl[0]) return;
@@ -492,13 +442,13 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
             float p[TR_SPX];
             dot4(p, w2q, hatt, TD, lane);
             const float v = to_lanes(p, lane);
-            if (lane < ns) publish(G + G_Q + lane * ADIM + r2, E + P_Q, v);
+            if (lane < ns) publish_xcd(G + G_Q + lane * ADIM + r2, E + P_Q, v);
         }
         if (att_on && wave < 2) {
             float v1[1];
-            const bool ok = sweep<1>(G + G_Q, E + P_Q, v1, [&](int i) { return sa * ADIM + wave * 64 + ln; }, tmo, fsl);
+            const bool ok = tr_sweep<1>(G + G_Q, E + P_Q, v1, [&](int i) { return sa * ADIM + wave * 64 + ln; }, tmo, fsl);
             q[wave * 64 + lane] = v1[0];
-            if (!ok && lane == 0) { ctl[0] = 1; fail(a.status, 4); }
+            if (!ok && lane == 0) { ctl[0] = 1; fail_word(a.status, 4); }
         }
         __syncthreads();
         if (ctl[0]) return;
@@ -535,16 +485,16 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
             __syncthreads();
             u64* gp = G + G_ATTP + (sa * TR_CPS + ka) * ATTP_W;
             if (tid < TD) {
-                publish(gp + tid, E + P_ATTP, red[tid] + red[280 + tid]);
+                publish_xcd(gp + tid, E + P_ATTP, red[tid] + red[280 + tid]);
             } else if (tid == TD) {
                 float sw = 0.f;
                 for (int k = 0; k < TR_PPC; ++k) sw += wj[k];  // index order
-                publish(gp + TD, E + P_ATTP, sw);
+                publish_xcd(gp + TD, E + P_ATTP, sw);
             } else if (tid == TD + 1) {
-                publish(gp + TD + 1, E + P_ATTP, wj[TR_PPC - 1]);  // next slice's alpha_{j-1}
+                publish_xcd(gp + TD + 1, E + P_ATTP, wj[TR_PPC - 1]);  // next slice's alpha_{j-1}
             } else if (tid == TD + 2) {
                 const int jt = La - 1 - j0;
-                publish(gp + TD + 2, E + P_ATTP, (jt >= 0 && jt < TR_PPC) ? wj[jt] : 0.f);
+                publish_xcd(gp + TD + 2, E + P_ATTP, (jt >= 0 && jt < TR_PPC) ? wj[jt] : 0.f);
             }
             MARK(4);
             // the sentence's first CU adds the 8 slices' partials in slice order
@@ -552,7 +502,7 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
                 float v8[TR_CPS];
                 bool ok = true;
                 if (tid < ATTP_W - 1)
-                    ok = sweep<TR_CPS>(G + G_ATTP + sa * TR_CPS * ATTP_W, E + P_ATTP, v8,
+                    ok = tr_sweep<TR_CPS>(G + G_ATTP + sa * TR_CPS * ATTP_W, E + P_ATTP, v8,
                                        [&](int i) { return i * ATTP_W + tid; }, tmo, fsl);
                 __syncthreads();  // red is rewritten below
                 if (tid < ATTP_W - 1) {
@@ -564,17 +514,17 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
 #pragma unroll
                         for (int k = 0; k < TR_CPS; ++k) red[280 + k] = v8[k];
                 }
-                if (!ok) { ctl[0] = 1; fail(a.status, 5); }
+                if (!ok) { ctl[0] = 1; fail_word(a.status, 5); }
                 __syncthreads();
                 if (ctl[0]) return;
                 const float W = red[TD];
                 u64* gc = G + G_CTXF + sa * CTXF_W;
-                if (tid < TD) publish(gc + tid, E + P_CTXF, red[tid] / W);           // context
-                else if (tid == TD) publish(gc + TD, E + P_CTXF, W);                  // normaliser
-                else if (tid == TD + 1) publish(gc + TD + 1, E + P_CTXF, red[TD + 2] / W);  // alpha[L-1]
+                if (tid < TD) publish_xcd(gc + tid, E + P_CTXF, red[tid] / W);           // context
+                else if (tid == TD) publish_xcd(gc + TD, E + P_CTXF, W);                  // normaliser
+                else if (tid == TD + 1) publish_xcd(gc + TD + 1, E + P_CTXF, red[TD + 2] / W);  // alpha[L-1]
                 else if (tid < TD + 2 + TR_CPS) {
                     const int k = tid - TD - 2;
-                    publish(gc + TD + 2 + k, E + P_CTXF, red[280 + k] / W);         // alpha at slice ends
+                    publish_xcd(gc + TD + 2 + k, E + P_CTXF, red[280 + k] / W);         // alpha at slice ends
                 }
                 MARK(5);
             }
@@ -582,7 +532,7 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
         // everyone: the contexts, normalisers, tails and boundary alphas of the group's sentences
         if (gon) {
             float v3[3];
-            const bool ok = sweep<3>(G + G_CTXF, E + P_CTXF, v3, [&](int i) {
+            const bool ok = tr_sweep<3>(G + G_CTXF, E + P_CTXF, v3, [&](int i) {
                 if (i < 2) return gs * CTXF_W + gf * 128 + ln + 64 * i;
                 return (gf == 1 && ln < 2 + TR_CPS) ? gs * CTXF_W + TD + ln : -1;
             }, tmo, fsl);
@@ -593,7 +543,7 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
                 if (lane == 1) tl[gs] = v3[2];
                 if (lane >= 2 && lane < 2 + TR_CPS) bnd[gs * TR_CPS + lane - 2] = v3[2];
             }
-            if (!ok && lane == 0) { ctl[0] = 1; fail(a.status, 6); }
+            if (!ok && lane == 0) { ctl[0] = 1; fail_word(a.status, 6); }
         }
         __syncthreads();
         if (ctl[0]) return;
@@ -620,14 +570,14 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
                        fmaf(wp[3], h.w, fmaf(wp[2], h.z, fmaf(wp[1], h.y, wp[0] * h.x)))))));
             }
             const float v = to_lanes(p, lane);
-            if (lane < ns) publish(G + G_DIN + lane * TD + U, E + P_DIN, v + bias[12]);
+            if (lane < ns) publish_xcd(G + G_DIN + lane * TD + U, E + P_DIN, v + bias[12]);
         }
         if (gon) {
             float v2[2];
-            const bool ok = sweep<2>(G + G_DIN, E + P_DIN, v2, [&](int i) { return gs * TD + gf * 128 + ln + 64 * i; }, tmo, fsl);
+            const bool ok = tr_sweep<2>(G + G_DIN, E + P_DIN, v2, [&](int i) { return gs * TD + gf * 128 + ln + 64 * i; }, tmo, fsl);
             din[gs * TD + gf * 128 + lane] = v2[0];
             din[gs * TD + gf * 128 + 64 + lane] = v2[1];
-            if (!ok && lane == 0) { ctl[0] = 1; fail(a.status, 7); }
+            if (!ok && lane == 0) { ctl[0] = 1; fail_word(a.status, 7); }
         }
         __syncthreads();
         if (ctl[0]) return;
@@ -674,21 +624,21 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
                     const float zg = sigmoid_cell(Z + bias[5 + 4 * g]);
                     const float ng = tanh_cell((N + bias[6 + 4 * g]) + rg * (Q + bias[7 + 4 * g]));
                     const float hn = (Hp[lane * TD + U] - ng) * zg + ng;
-                    publish(gg + lane * TD + U, tg, hn);
-                    publish(gg + TR_SPX * TD + lane * TD + U, tg, hn + X[lane * TD + U]);
+                    publish_xcd(gg + lane * TD + U, tg, hn);
+                    publish_xcd(gg + TR_SPX * TD + lane * TD + U, tg, hn + X[lane * TD + U]);
                 }
             }
             MARK(13 + g);
             if (gon) {
                 float v4[4];
-                const bool ok = sweep<4>(gg, tg, v4, [&](int i) {
+                const bool ok = tr_sweep<4>(gg, tg, v4, [&](int i) {
                     return (i < 2 ? 0 : TR_SPX * TD) + gs * TD + gf * 128 + ln + 64 * (i & 1);
                 }, tmo, fsl);
                 Hn[gs * TD + gf * 128 + lane] = v4[0];
                 Hn[gs * TD + gf * 128 + 64 + lane] = v4[1];
                 Dn[gs * TD + gf * 128 + lane] = v4[2];
                 Dn[gs * TD + gf * 128 + 64 + lane] = v4[3];
-                if (!ok && lane == 0) { ctl[0] = 1; fail(a.status, 10 + g); }
+                if (!ok && lane == 0) { ctl[0] = 1; fail_word(a.status, 10 + g); }
             }
             __syncthreads();
             if (ctl[0]) return;
@@ -710,8 +660,8 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
                 const int b = b0 + lane;
                 const float o0 = m0 < nmel ? sigmoidf_(v0 + bm0) : 0.f;
                 const float o1 = m1 < nmel ? sigmoidf_(v1 + bm1) : 0.f;
-                publish(G + G_MEL + lane * TR_NMEL_MAX + m0, E + P_MEL, o0);
-                publish(G + G_MEL + lane * TR_NMEL_MAX + m1, E + P_MEL, o1);
+                publish_xcd(G + G_MEL + lane * TR_NMEL_MAX + m0, E + P_MEL, o0);
+                publish_xcd(G + G_MEL + lane * TR_NMEL_MAX + m1, E + P_MEL, o1);
                 if (t < a.hist_cap) {
                     float* row = a.mel_hist + (QUEUE ? b * a.hist_ld : (int64_t)b * a.hist_cap * nmel) + (int64_t)t * nmel;
                     if (m0 < nmel) row[m0] = o0;
@@ -723,12 +673,12 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
         if (!QUEUE) {
             if (gon) {
                 float v4[4];
-                const bool ok = sweep<4>(G + G_MEL, E + P_MEL, v4, [&](int i) {
+                const bool ok = tr_sweep<4>(G + G_MEL, E + P_MEL, v4, [&](int i) {
                     return gs * TR_NMEL_MAX + gf * 256 + ln + 64 * i;
                 }, tmo, fsl);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) mel[gs * TR_NMEL_MAX + gf * 256 + lane + 64 * i] = v4[i];
-                if (!ok && lane == 0) { ctl[0] = 1; fail(a.status, 12); }
+                if (!ok && lane == 0) { ctl[0] = 1; fail_word(a.status, 12); }
             }
         } else {
             // _update_memory_queue (:396-404): queue = cat(queue[nmel:], output).  The ranges overlap
@@ -736,7 +686,7 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
             float v4[4], keep[4];
             float* qs = mel + gs * TR_NMEL_MAX;
             if (gon) {
-                const bool ok = sweep<4>(G + G_MEL, E + P_MEL, v4, [&](int i) {
+                const bool ok = tr_sweep<4>(G + G_MEL, E + P_MEL, v4, [&](int i) {
                     return gs * TR_NMEL_MAX + gf * 256 + ln + 64 * i;
                 }, tmo, fsl);
 #pragma unroll
@@ -744,7 +694,7 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
                     const int k = gf * 256 + lane + 64 * i;
                     keep[i] = k < qo ? qs[k + nmel] : 0.f;  // k + nmel < nq <= TR_NMEL_MAX
                 }
-                if (!ok && lane == 0) { ctl[0] = 1; fail(a.status, 12); }
+                if (!ok && lane == 0) { ctl[0] = 1; fail_word(a.status, 12); }
             }
             __syncthreads();
             if (gon) {
@@ -784,7 +734,7 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
                         a.n_steps[b] = t1;
                     }
                 }
-                publish(G + G_PRE1 + TR_SPX * T_PRE1 + s, E + P_PRE1, nd ? 0.f : 1.f);
+                publish_xcd(G + G_PRE1 + TR_SPX * T_PRE1 + s, E + P_PRE1, nd ? 0.f : 1.f);
             }
         }
         // prenet L1 of step t+1, row U (memory = this output, or the queue it now ends: :396-404)
@@ -799,7 +749,7 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
                        fmaf(wa.w, xa_.w, fmaf(wa.z, xa_.z, fmaf(wa.y, xa_.y, wa.x * xa_.x)))))));
             }
             const float v = to_lanes(p, lane);
-            if (lane < ns) publish(G + G_PRE1 + lane * T_PRE1 + U, E + P_PRE1, fmaxf(v + bias[13], 0.f));
+            if (lane < ns) publish_xcd(G + G_PRE1 + lane * T_PRE1 + U, E + P_PRE1, fmaxf(v + bias[13], 0.f));
         }
         MARK(11);
     }
