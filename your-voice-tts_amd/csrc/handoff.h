@@ -217,7 +217,26 @@ __device__ __forceinline__ bool sweep_one(__amdgpu_buffer_rsrc_t r, int slot, un
         if (RES_SLEEP) __builtin_amdgcn_s_sleep(RES_SLEEP);
     }
 }
-
+// sweep_one with a second granule on the lanes whose `slot2` >= 0 (tag `tag2`, value v2): a word
+// published long before the awaited granules, taken in the same bounded sweep.  Both loads of a
+// poll are issued before either is consumed, the early word's first (vmcnt counts in order: its
+// round trip lies inside the awaited granule's).  A lane without a second granule loads past the
+// buffer (no access).  in2: this lane's second tag was in at the last poll (the caller's fail code).
+__device__ __forceinline__ bool sweep_one_and(__amdgpu_buffer_rsrc_t r, int slot, unsigned tag, float& v, int slot2,
+                                              unsigned tag2, float& v2, bool& in2, long long tmo) {
+    const long long t_end = (long long)wall_clock64() + tmo;
+    const int off2 = slot2 >= 0 ? slot2 * 8 : OOB_OFF;
+    for (int spin = 0;; ++spin) {
+        const u32x2 y = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(r, off2, 0, SC1_VOLATILE));
+        const u32x2 x = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(r, slot * 8, 0, SC1_VOLATILE));
+        v = __uint_as_float(x.x);
+        v2 = __uint_as_float(y.x);
+        in2 = (slot2 < 0) | (y.y == tag2);
+        if (__all((x.y == tag) & in2)) return true;
+        if ((spin & 31) == 0 && (long long)wall_clock64() > t_end) return false;
+        if (RES_SLEEP) __builtin_amdgcn_s_sleep(RES_SLEEP);
+    }
+}
 
 // Poll NP consecutive granule pairs from even slot `base` (thread i of the THREADS-wide workgroup: pairs i, i + THREADS, ...): every
 // poll issues all of the thread's loads before one wait; the values go to dst[2p], dst[2p + 1]

@@ -52,7 +52,8 @@ constexpr int RES_LMAX = 256;
 // GR_QX: per-XCD query half-rows [8][128 rows][2] (synthesis form: full-evaluation steps only);
 // GR_CTXX: per-XCD [8][528]: context + tail (general form) | energy partials [16 slots][32 CUs]
 // (synthesis form);
-// GR_P1X: per-XCD prenet-1 rows + continue flag [8][264] (slot 256 = flag).
+// GR_P1X: per-XCD prenet-1 rows + continue flag [8][264] (slot 256 = flag; synthesis form: step
+// t's flag is published behind step t+1's prenet-2 row and read at its energy gather, under step t's tag).
 // GR_EX: per-XCD attention energies [8][RES_LMAX] (general attention form: each CU of the XCD
 // publishes the energies of its positions, every CU gathers all L).
 constexpr int GR_HATT = 576, GR_HDEC = 2304, GR_PRE2X = 3328, GR_SETUP = 5376, GR_QX = 5632, GR_CTXX = 7680,
@@ -130,7 +131,8 @@ struct ResArgs {
     float* align_hist;
     unsigned long long* gran;  // [2][GR_TOTAL], zeroed before every launch
     int* status;               // [0]: 0 ok, else the id of the wait that timed out (10: the energy
-                               // partials' gather, synthesis form)
+                               // partials' gather, synthesis form; 1 there: the continue flag
+                               // taken in the same sweep)
     // s_sleep(4) counts (~0.12 us each) before the first poll of a gather: a poll storm from every CU
     // slows the hand-off it waits for (device-wide h_att / h_dec; XCD-local pre1, prenet-2; the
     // general form's context)
@@ -147,9 +149,10 @@ constexpr int RES_PHASES = 16;
 // (P1, B1, h_att published, B3, B4, h_dec published, B6, pre1 row published; synthesis form: partials
 // published, partials gathered, A2 (candidate energies); general form: query row published [8],
 // context published [11]; both forms: loop-top work done on wave 0 [12] and on wave 3 [13], ahead
-// of the pre1 poll; synthesis form: next step's attention operands issued, wave 6 [14]; the continue
-// flag published on a stop CU, wave 3, and on every other CU the pre1 rows gathered, wave 0 on the
-// CUs of even rank and wave 1 on the odd [11]; the previous step's continue flag gathered, wave 2 [15])
+// of the pre1 poll; synthesis form: next step's attention operands issued, wave 6 [14]; the previous
+// step's continue flag published on a stop CU, wave 5, behind its prenet-2 row, and on every
+// other CU the pre1 rows gathered, wave 0 on the CUs of even rank and wave 1 on the odd [11]; the
+// previous step's continue flag gathered with the energy partials, wave 2 [15])
 constexpr int RES_TRACE_STEPS = 64, RES_TRACE_EV = 16;
 constexpr size_t RES_PROF_LL = 2 * RES_PHASES + (size_t)RES_CUS * RES_TRACE_STEPS * RES_TRACE_EV;
 

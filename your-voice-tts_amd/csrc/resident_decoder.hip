@@ -6,25 +6,30 @@
 //      h_dec_{t-1} while pre1 is in flight; synthesis form: nothing, its partials ran inside the
 //      device-wide waits of steps 4 and 10 (step 0's attention partial ahead of the loop)
 //   2. waves 0-1: wait pre1_t (general form: wave 2 the continue flag); prenet-2 row c, publish;
-//      gather the 256 rows; synthesis form: wave 2 sweeps the previous step's continue flag behind
-//      its prenet-2 row and the loop ends after B1 (the flag leaves the stop CU behind every row)
-//   3. prenet part, row sums, LSTM cell of units 4c..4c+3, publish h_att_t   (tacotron2.py:195-197)
+//      gather the 256 rows; synthesis form, meanwhile, on the XCD's stop CU (rank 0), wave 5: the
+//      stop row, sigmoid and stop rule of step t-1 -> XCD-local continue flag (tacotron2.py:219-224,
+//      257-277; xh_dec, xctx still hold h_dec_{t-1}, ctx_{t-1} and its tail); its continue check: step 7
+//   3. prenet part, row sums, LSTM cell of units 4c..4c+3, publish h_att_t   (tacotron2.py:195-197);
+//      synthesis form: lanes 0-3 keep the (c, h) the cell replaces, for the exit
 //   4. synthesis form: decoder-LSTM partial over h_dec_{t-1} (LDS weights) as the first-poll delay;
-//      gather h_att_t; 5. four query rows of the XCD's copy (common_layers.py:179); synthesis form:
+//      gather h_att_t;
+//   5. four query rows of the XCD's copy (common_layers.py:179); synthesis form:
 //      rows rank + 32 m -> lane `rank`'s partial of the 16 candidate energies, XCD-local publish
 //   6. decoder-LSTM partial over h_att_t                                   (LDS weights)
-//   7. synthesis form, every CU: gather the XCD's 16 x 32 partials, energies, sigmoid, forward
-//      attention + mask, the five weights, the 512 context channels into its own LDS, the tail
+//   7. synthesis form, every CU: gather the XCD's 16 x 32 partials (wave 2 with them the previous
+//      step's continue flag: the loop ends after A2, so the ending step runs 2-7 once for a step
+//      that does not exist and the exit restores the attention LSTM's state), energies, sigmoid,
+//      forward attention + mask, the five weights, the 512 context channels into its own LDS, the tail
 //      (common_layers.py:178-182, 199-223, 239-253); general form: 7' below, 8. gather ctx_t
 //   9. context part, cell, publish h_dec_t                                (tacotron2.py:206-208)
 //  10. synthesis form: step t+1's attention-LSTM partial over [ctx_t | h_att_t] (VGPR weights) as
 //      the first-poll delay, carried to step 3 of t+1; gather h_dec_t (the prenet-1 row weights of
 //      step 11 in flight from the XCD's L2);
-//  11. every wave: one folded prenet-1 row of this XCD's copy -> XCD-local publish; the XCD's
-//      stop CU (rank 0), wave 3: the stop row (synthesis form: in a pass of its own behind the
-//      publish) -> sigmoid + stop rule -> XCD-local continue flag
-//      (tacotron2.py:214-224, 256-277).  Mel row c of step t is written by wave 4 during step
-//      t+1's h_att gather (after the loop for the last step).
+//  11. every wave: one folded prenet-1 row of this XCD's copy -> XCD-local publish
+//      (tacotron2.py:214-218); general form, the XCD's stop CU (rank 0), wave 3: the stop row in
+//      the same pass -> sigmoid + stop rule -> XCD-local continue flag (:219-224, 256-277).  Mel
+//      row c of step t is written by wave 4 during step t+1's h_att gather (general form: after
+//      the loop for the last step; synthesis form: the ending step's).
 //  12. synthesis form, waves 3-7 (no poll of theirs before step t+1's h_att gather): step t+1's
 //      attention operands, the entering encoder row and P at the candidate positions, in flight
 //      during the pre1 and prenet-2 edges; those of the polling waves 0-2 reach them through LDS
@@ -201,6 +206,8 @@ constexpr int SM_RQ = 4 * 64 * 4;          // synthesis form: attention scratch 
 constexpr int SM_RM = 2 * 6 * 64 * 4 + 2 * 256;  // mel row c, stop row: [2][6][64] float4 | general form: cumulative weights
 constexpr int SM_PROF = 2 * 16;            // RES_PHASES tick accumulators (long long)
 constexpr int RES_POLL_WAVES = 3;           // waves 0-2 poll between B6 and the h_att gather (pre1, prenet-2)
+constexpr int RES_STOP_WAVE = 5;            // synthesis form: the stop CU's wave of the stop row and rule
+static_assert(RES_STOP_WAVE >= RES_POLL_WAVES && RES_STOP_WAVE != 4 && RES_STOP_WAVE < RES_WAVES, "no polling wave, not the mel row's");
 constexpr int SM_OPR = RES_POLL_WAVES * 64;  // synthesis form: their channels of the entering encoder row
 constexpr int SM_FLOATS = SM_WDL + HATT + HDEC + (ENC + 16) + PRE + ADIM + 16 + 16 + SM_ST + SM_RQ + SM_RM + SM_PROF + PRE + SM_OPR;
 static_assert(SM_FLOATS * 4 <= 160 * 1024, "the CU's LDS");
@@ -504,6 +511,36 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         sm_ = wave_sum_dpp(sm_);
         if (lane == 0 && tt < a.hist_cap) a.mel_hist[(int64_t)tt * a.nmel + c] = sm_ + st[48];
     };
+    // stopnet + stop rule of step tt from the stop row's sum ss (tacotron2.py:219-224, 257-277), as
+    // EPI_MEL_FUSED rule 0, by one lane of the XCD's stop CU; the continue flag goes to `gflag`
+    // under `tag`, XCD-locally.  Every XCD's stop CU decides identically, the logging XCD writes
+    // the outputs.  The tail: gathered beside the context (general form), this CU's own (synthesis
+    // form).  (A macro for the reason given at the partials below.)
+#define RES_STOP_RULE(tt, ss, gflag, tag)                                                                           \
+    {                                                                                                               \
+        const float stv = sigmoidf_((ss) + st[49]);                                                                 \
+        if (xlog && (tt) < a.hist_cap) a.stop_hist[(tt)] = stv;                                                     \
+        const float tail = xctx[ENC];                                                                               \
+        int* sst = reinterpret_cast<int*>(st);                                                                      \
+        const int f1 = sst[50] | ((tail > 0.8f && (tt) > L) ? 1 : 0);                                               \
+        sst[50] = f1;                                                                                               \
+        int nd = 0;                                                                                                 \
+        if (f1 && (tt) > 2 * L) {                                                                                   \
+            sst[51] += 1;                                                                                           \
+            if (sst[51] > 20) nd = 1;                                                                               \
+        } else if ((tt) + 1 == a.max_steps) {                                                                       \
+            nd = 1;                                                                                                 \
+        }                                                                                                           \
+        if (!nd && (tt) + 1 >= a.hist_cap) { /* cannot happen: the rule stops by max_steps + 20 */                  \
+            nd = 1;                                                                                                 \
+            fail(a.status, 100);                                                                                    \
+        }                                                                                                           \
+        if (nd && xlog) {                                                                                           \
+            a.done[0] = 1;                                                                                          \
+            a.n_steps[0] = (tt) + 1;                                                                                \
+        }                                                                                                           \
+        publish_xcd((gflag), (tag), nd ? 0.f : 1.f);                                                                \
+    }
     // The two LSTMs' partials over the previous step's state (chunk order, accumulator parity and
     // the final add are pinned: the resident fixtures are bitwise).  Macros, not lambdas: the
     // general form's kernels then compile to the instructions they had with this text at the loop top.
@@ -533,6 +570,9 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
     // is formed here from the initial context and h_att (a continued run: the carried state)
     float acc_a_next = 0.f;
     if constexpr (!GEN) RES_ATT_PARTIAL(acc_a_next)
+    // synthesis form, lanes 0-3 of wave 0: the attention LSTM's (c, h) of units 4c..4c+3 before
+    // the current step's cell, and the current h (the deferred exit writes the kept pair)
+    float c_att_keep = 0.f, h_att_keep = 0.f, h_att_last = 0.f;
     int t = 0;
     for (;; ++t) {
         u64* G = a.gran + (t & 1) * GR_TOTAL;          // this step's granules
@@ -551,8 +591,7 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         const unsigned EP6 = ((a.salt << 14) | (((unsigned)(t - 1) & 2047u) << 3)) + 6u;
         // 1) general form: both LSTMs' recurrent partials while pre1 is in flight.  The synthesis
         //    form formed them inside the previous device-wide waits (steps 4 and 10): its loop top
-        //    holds nothing but the pre1 poll, so a stop CU's stop row and rule (step 11), which
-        //    precede it on wave 3, run while the other waves wait for the pre1 rows
+        //    holds nothing but the pre1 poll
         float acc_a, acc_d;
         if constexpr (GEN) {
             RES_ATT_PARTIAL(acc_a)
@@ -565,10 +604,9 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         // 2) prenet layer 2: wave 0 gathers this XCD's pre1_t (+ the previous step's continue flag);
         //    every wave computes its row of this XCD's copy, publishes it XCD-locally; wave 0 gathers
         // (waves 0, 1: the 256 rows as pairs; wave 2, lane 0: the flag.  The synthesis form's P1
-        // waits for the rows alone: the flag leaves the stop CU behind the stop row and the rule,
-        // 0.4 us after the XCD's last row (traced), and is 1 on all steps but the last, so its
-        // wave 2 sweeps it behind its prenet-2 row, one XCD-local edge later, and the loop ends
-        // after B1)
+        // waits for the rows alone: the previous step's stop row and rule run on its stop CU
+        // behind this step's prenet-2 row (below), the flag is 1 on all steps but the last, so
+        // its wave 2 takes it in the energy partials' sweep and the loop ends after A2)
         constexpr bool DEFER = !GEN;
         if (wave < (DEFER ? 2 : 3)) {
             const int gp = s_1 + ((t & 1) ^ 1) * GR_TOTAL;
@@ -591,9 +629,6 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
                 } else {
                     ok = sweep_pair(rg, lane == 0 ? gp + PRE : -1, false, EP6, p0, p1, tmo);
                     if (lane == 0 && ok && p0 == 0.f) flags[0] = 1;
-                    if constexpr (!GEN) {
-                        if (lane == 0) { RES_EV(t, 15) }
-                    }
                 }
             }
             RES_MARK(0);
@@ -601,9 +636,11 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         }
         __syncthreads();  // P1
         if (tid == 0) { RES_EV(t, 0) }
-        // (the synthesis form runs the prenet-2 edge of a step that does not exist once, on the
-        // ending step: it touches xp1, xpre and this step's prenet-2 granules, which nothing reads
-        // afterwards, and its gather completes, every CU of the XCD having read the same flag)
+        // (the synthesis form runs P1 to A2 of a step that does not exist once, on the ending step.
+        // Every CU of the device reads the same flag, so its gathers complete.  Of what it touches
+        // only the attention LSTM's (c, h) outlives the loop, and the exit restores them from the
+        // values kept in step 3; xp1, xpre, xh_att, xrow, xpt, gates, scr, an, candv, acc_a,
+        // acc_d, ex / erow and the granules under this step's tags are read by nothing afterwards)
         if (DEFER ? flags[1] : (flags[0] | flags[1])) break;
         {
             const float4 x = ld4(xp1 + lane * 4);
@@ -613,15 +650,35 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
                 if (lane == 0) publish_xcd(gx + r0, E + 1, fmaxf(s0 + bp2, 0.f));
             }
             RES_MARK(1);
-            if constexpr (DEFER) {
-                // the previous step's continue flag (same granule, tag and bound as ahead of P1)
-                if (wave == 2 && t > 0) {
-                    float p0 = 0.f, p1 = 0.f;
-                    const bool ok = sweep_pair(rg, lane == 0 ? s_1 + ((t & 1) ^ 1) * GR_TOTAL + PRE : -1, false, EP6, p0, p1, tmo);
+            if constexpr (!GEN) {
+                // the XCD's stop CU, wave RES_STOP_WAVE, behind its prenet-2 row: the stop row, sigmoid
+                // and rule of step t-1, while waves 0-1 gather the prenet-2 rows (this wave's next
+                // poll is the h_att gather).  Its operands are still here: xh_dec = h_dec_{t-1}
+                // until B3, xctx = ctx_{t-1} until the context write behind A2, xctx[ENC] the tail
+                // wave 7 left after B5.  The flag goes to step t-1's granule under its tag; this
+                // step's wave 2 takes it behind B3, with the energy partials.  Two rounds of three
+                // chunks, a round's LDS reads in flight together (as step 11)
+                if (stop_cu && wave == RES_STOP_WAVE && t > 0) {
+                    const float4* wsr = reinterpret_cast<const float4*>(rm) + 6 * 64 + lane;
+                    float ss = 0.f;
+#pragma unroll 1
+                    for (int h = 0; h < 6; h += 3) {
+                        float4 wv[3], xx[3];
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) {
+                            const int i = h + j;
+                            wv[j] = wsr[i * 64];
+                            xx[j] = i < 4 ? ld4(xh_dec + i * 256 + lane * 4) : ld4(xctx + (i - 4) * 256 + lane * 4);
+                        }
+                        pin3(wv[0], wv[1], wv[2]);
+                        pin3(xx[0], xx[1], xx[2]);
+#pragma unroll
+                        for (int j = 0; j < 3; ++j) ss = dot4(wv[j], xx[j], ss);
+                    }
+                    ss = wave_sum_dpp(ss);
                     if (lane == 0) {
-                        if (!ok) { flags[1] = 1; fail(a.status, 1, t); }
-                        else if (p0 == 0.f) flags[0] = 1;
-                        RES_EV(t, 15)
+                        RES_STOP_RULE(t - 1, ss, a.gran + ((t & 1) ^ 1) * GR_TOTAL + s_1 + PRE, EP6)
+                        RES_EV(t, 11)
                     }
                 }
             }
@@ -636,7 +693,7 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         }
         __syncthreads();  // B1
         if (tid == 0) { RES_EV(t, 1) }
-        if (DEFER ? (flags[0] | flags[1]) : flags[1]) break;
+        if (flags[1]) break;
         RES_MARK(2);
         // 3) prenet part, cell
 #pragma unroll
@@ -655,10 +712,17 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         RES_MARK(3);
         if (tid < 16) {
             float cs = st[32 + (tid & 3)];
+            // (synthesis form: the ending step runs this cell for a step that does not exist; lanes
+            // 0-3 keep the last real step's (c, h) for the exit)
+            if constexpr (!GEN) c_att_keep = cs;
             const float h = lstm_cell16(gates[tid] + st[tid], cs);
             if (tid < 4) {
                 st[32 + tid] = cs;
                 st[40 + tid] = h;
+                if constexpr (!GEN) {
+                    h_att_keep = h_att_last;
+                    h_att_last = h;
+                }
                 publish_agent(G + GR_HATT + 4 * c + tid, E + 2, h);
                 if (tid == 0) { RES_EV(t, 2) }
             }
@@ -971,9 +1035,25 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
                 // every wave gathers its two slots' 32 partials, one granule per lane: lane (sl, sub)
                 // holds CU sub's partial of slot sl, the lane order of the sum below
                 for (int i = 0; i < a.sleep_q; ++i) __builtin_amdgcn_s_sleep(1);
+                // wave 2, lane 0, in the same sweep: the previous step's continue flag, which its stop
+                // CU published behind this step's prenet-2 row, two edges ago (same granule, tag
+                // and bound as when it was swept ahead of P1: status 1 with the step)
                 float part = 0.f;
-                const bool ok = sweep_one(rg, s_c + (t & 1) * GR_TOTAL + res_part_slot(sl, sub), E + 3, part, tmo);
-                if (!ok && lane == 0) { flags[1] = 1; fail(a.status, 10, t); }
+                const int pslot = s_c + (t & 1) * GR_TOTAL + res_part_slot(sl, sub);
+                if (wave == 2) {
+                    float fv = 1.f;
+                    bool fin = true;
+                    const bool ok = sweep_one_and(rg, pslot, E + 3, part, lane == 0 ? s_1 + ((t & 1) ^ 1) * GR_TOTAL + PRE : -1,
+                                                  EP6, fv, fin, tmo);
+                    if (!ok && lane == 0) { flags[1] = 1; fail(a.status, fin ? 10 : 1, t); }
+                    if (lane == 0) {
+                        if (ok && fv == 0.f) flags[0] = 1;
+                        RES_EV(t, 15)
+                    }
+                } else {
+                    const bool ok = sweep_one(rg, pslot, E + 3, part, tmo);
+                    if (!ok && lane == 0) { flags[1] = 1; fail(a.status, 10, t); }
+                }
                 if (tid == 0) { RES_EV(t, 9) }
                 RES_MARK(6);
                 const float e = sum32_dpp(part);
@@ -984,7 +1064,10 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
                 }
                 __syncthreads();  // A2
                 if (tid == 0) { RES_EV(t, 10) }
-                if (flags[1]) break;
+                // the loop's end: the ending step stops here, ahead of the choice of a full
+                // evaluation and of the context write (xctx, abuf, n, the decoder LSTM's state and
+                // a.pre1 stay the last real step's)
+                if (flags[0] | flags[1]) break;
                 RES_MARK(14);
                 // one LDS read per lane (slot lane % 16), the max by DPP, the window slots 1-4 (they
                 // hold exactly an[clo + k]: the same lane wrote both) by readlane: no chain of
@@ -1197,12 +1280,12 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         RES_MARK(12);
         long long m0 = 0;  // prenet-1 / mel / stop row phase timing (wave 2, lane 0)
         if (prof && tid == 128) m0 = (long long)wall_clock64();
-        // 11) this wave's folded prenet-1 row of step t+1 (XCD copy) and, on the stop CU's wave 3,
-        //     the stop row: the general form in the same pass; the synthesis form in a pass of its
-        //     own behind the publish (the same six products in the same order), so that the row the
-        //     XCD's 32 CUs wait for leaves with the others
+        // 11) this wave's folded prenet-1 row of step t+1 (XCD copy); the general form, on the stop
+        //     CU's wave 3, also the stop row in the same pass and then the rule.  The synthesis
+        //     form's step 11 is this one pass on every wave of every CU: its stop row and rule run
+        //     in step t+1, behind the prenet-2 row (step 2)
         {
-            const bool stw = stop_cu && wave == 3;
+            const bool stw = GEN && stop_cu && wave == 3;
             const float4* wsr = reinterpret_cast<const float4*>(rm) + 6 * 64 + lane;
             float s = 0.f, ss = 0.f;
             if constexpr (!GEN) {
@@ -1242,52 +1325,8 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
                 if (xlog) a.pre1[r0] = p;  // the next step's layer 1 (continuous mode reads it)
             }
             if (stw) {
-                if constexpr (!GEN) {
-                    asm volatile("" ::: "memory");  // (the stop row's LDS reads stay behind the publish)
-#pragma unroll 1
-                    for (int h = 0; h < 6; h += 3) {
-                        float4 wv[3], xx[3];
-#pragma unroll
-                        for (int j = 0; j < 3; ++j) {
-                            const int i = h + j;
-                            wv[j] = wsr[i * 64];
-                            xx[j] = i < 4 ? ld4(xh_dec + i * 256 + lane * 4) : ld4(xctx + (i - 4) * 256 + lane * 4);
-                        }
-                        pin3(wv[0], wv[1], wv[2]);
-                        pin3(xx[0], xx[1], xx[2]);
-#pragma unroll
-                        for (int j = 0; j < 3; ++j) ss = dot4(wv[j], xx[j], ss);
-                    }
-                }
                 ss = wave_sum_dpp(ss);
-                if (lane == 0) {
-                    // stopnet + stop rule (tacotron2.py:219-224, 257-277), as EPI_MEL_FUSED rule 0;
-                    // every XCD's stop CU decides identically, the logging XCD writes the outputs
-                    const float stv = sigmoidf_(ss + st[49]);
-                    if (xlog && t < a.hist_cap) a.stop_hist[t] = stv;
-                    // the tail: gathered beside the context (general form), this CU's own (synthesis form)
-                    const float tail = xctx[ENC];
-                    int* sst = reinterpret_cast<int*>(st);
-                    const int f1 = sst[50] | ((tail > 0.8f && t > L) ? 1 : 0);
-                    sst[50] = f1;
-                    int nd = 0;
-                    if (f1 && t > 2 * L) {
-                        sst[51] += 1;
-                        if (sst[51] > 20) nd = 1;
-                    } else if (t + 1 == a.max_steps) {
-                        nd = 1;
-                    }
-                    if (!nd && t + 1 >= a.hist_cap) {  // cannot happen: the rule stops by max_steps + 20
-                        nd = 1;
-                        fail(a.status, 100);
-                    }
-                    if (nd && xlog) {
-                        a.done[0] = 1;
-                        a.n_steps[0] = t + 1;
-                    }
-                    publish_xcd(g1 + PRE, E + 6, nd ? 0.f : 1.f);
-                    if constexpr (!GEN) { RES_EV(t, 11) }
-                }
+                if (lane == 0) RES_STOP_RULE(t, ss, g1 + PRE, E + 6)
             }
         }
         if (prof && tid == 128) pacc[13] += (long long)wall_clock64() - m0;
@@ -1322,14 +1361,19 @@ __global__ __launch_bounds__(RES_THREADS, 1) void resident_decoder_kernel(const 
         }
     }
     if (flags[1]) return;
-    if (wave == 4 && t > 0) mel_row(t - 1);  // the last step's mel row (its h_att gather never came)
+    // the last step's mel row: the general form's h_att gather never came; the synthesis form
+    // wrote it inside the ending step's h_att wait (t >= 1 there: step 0 has no flag to end on)
+    if constexpr (GEN) {
+        if (wave == 4 && t > 0) mel_row(t - 1);
+    }
     if (prof && tid == 0)
         for (int k = 0; k < RES_PHASES; ++k) a.prof[(c == 0 ? 0 : 1) * RES_PHASES + k] = pacc[k];
-    // the last step t-1 leaves its state where the multi-launch path's would be
+    // the last step t-1 leaves its state where the multi-launch path's would be (synthesis form:
+    // the attention LSTM's from the kept registers, the ending step's cell having run over st)
     const int pl = (t - 1) & 1;
     if (tid < 4) {
-        a.h_att[pl * a.hps + 4 * c + tid] = st[40 + tid];
-        a.c_att[4 * c + tid] = st[32 + tid];
+        a.h_att[pl * a.hps + 4 * c + tid] = GEN ? st[40 + tid] : h_att_keep;
+        a.c_att[4 * c + tid] = GEN ? st[32 + tid] : c_att_keep;
         a.h_dec[pl * a.hps + 4 * c + tid] = st[44 + tid];
         a.c_dec[4 * c + tid] = st[36 + tid];
     }
