@@ -739,6 +739,61 @@ tts_status tts_lstm_backward(tts_lstm* l, const float* x, const int32_t* lens, i
                              float* const* grad_w_ih, float* const* grad_w_hh, float* const* grad_b_ih,
                              float* const* grad_b_hh, void* stream);
 
+/* ---------------------------------------------------------------- trainable conv-BN block (convbn_train.hip)
+ * The reference's ConvBNBlock (layers/tacotron2.py:9-27): Conv1d(k = 5, padding = 2) -> BatchNorm1d ->
+ * ReLU | Tanh | nothing -> Dropout, as Encoder.convolutions (:52-55) and Postnet.convolutions (:30-45) run it
+ * in training, with its whole backward; with training == 0 it normalises with the running statistics.
+ * Every product is an exact fp32 MFMA chain, the per-channel sums are fp64 partials folded in a fixed order,
+ * nothing is accumulated with atomics: the same operands give the same bits.  The handle owns the repacked
+ * weights and the workspaces, grown on demand; all calls on one handle must be ordered on one stream.  The
+ * reserve belongs to the caller, so several forwards may be outstanding before their backwards.  No call
+ * waits for the stream or copies to or from the host; a workspace that has to grow is freed and allocated
+ * again, which waits for the device that once.  Activations are [B][C][T] contiguous fp32 with 4-byte
+ * alignment only; T is arbitrary. */
+typedef struct tts_convbn tts_convbn;
+
+/* act: 0 none, 1 relu, 2 tanh (else INVALID).  UNSUPPORTED unless kernel_size == 5 and cin, cout are positive
+ * multiples of 16. */
+tts_status tts_convbn_create(int cin, int cout, int kernel_size, int act, tts_convbn** out);
+void tts_convbn_destroy(tts_convbn* h);
+
+/* [dev] W [cout][cin][5] (net.0.weight), bias [cout] (net.0.bias), gamma, beta [cout] (net.1.weight, .bias).
+ * Repacks W on the stream for the forward, grad_x (taps flipped, transposed) and keeps copies of the three
+ * vectors; call it again whenever the parameters have changed. */
+tts_status tts_convbn_set_weights(tts_convbn* h, const float* W, const float* bias, const float* gamma,
+                                  const float* beta, void* stream);
+
+/* Floats of the reserve a training forward of this shape fills: y = conv(x) + bias [B][cout][T], the batch
+ * mean and 1 / sqrt(var + eps) per channel, the dropout scale.  0 for a null handle or a B or T <= 0. */
+int64_t tts_convbn_reserve_floats(const tts_convbn* h, int B, int T);
+
+/* self.net(x) (layers/tacotron2.py:25-27).
+ *   x        [dev]  [B][cin][T]
+ *   mask     [dev]  uint8 [B][cout][T], 1 = keep (training only; not read otherwise)
+ *   p_keep_scale    1 / (1 - p) of the dropout (training only)
+ *   running_mean, running_var [dev] [cout]: training: updated in place with `momentum` (the variance
+ *            unbiased, n / (n - 1)); else the statistics that normalise
+ *   out      [dev]  [B][cout][T]; an element with mask == 0 is +0.0
+ *   reserve  [dev]  tts_convbn_reserve_floats(h, B, T) floats, or NULL (no backward will follow; out is bitwise
+ *            the same); not used with training == 0
+ * Batch statistics run over all B * T positions of a channel (biased variance).
+ * INVALID before any launch, with nothing written: a null handle, x, out or running buffer; weights not set;
+ * B or T <= 0; in training a null mask or B * T == 1.  5 launches in training, 4 otherwise. */
+tts_status tts_convbn_forward(tts_convbn* h, const float* x, int B, int T, const uint8_t* mask, float p_keep_scale,
+                              float* running_mean, float* running_var, double momentum, double eps, int training,
+                              float* out, float* reserve, void* stream);
+
+/* The backward of that training forward for an upstream gradient of out.
+ *   x, B, T, mask  as the forward had them; reserve: what it wrote
+ *   grad_out [dev]  [B][cout][T]
+ *   grad_x   [dev]  [B][cin][T];  grad_W [cout][cin][5];  grad_bias, grad_gamma, grad_beta [cout]
+ * Gradients are WRITTEN, not accumulated.  Any of the five may be NULL; that product is skipped.  The weights
+ * are those of the last tts_convbn_set_weights: they must be the forward's.  INVALID before any launch: as
+ * the forward; a null reserve, mask or grad_out.  At most 10 launches. */
+tts_status tts_convbn_backward(tts_convbn* h, const float* x, int B, int T, const float* reserve, const uint8_t* mask,
+                               const float* grad_out, float* grad_x, float* grad_W, float* grad_bias, float* grad_gamma,
+                               float* grad_beta, void* stream);
+
 const char* tts_last_error(void);
 const char* tts_version(void);
 

@@ -49,6 +49,8 @@ EXPORTS = (
     "tts_optim_decay", "tts_optim_adam", "tts_optim_step",
     "tts_lstm_create", "tts_lstm_destroy", "tts_lstm_set_weights", "tts_lstm_reserve_floats", "tts_lstm_forward",
     "tts_lstm_backward",
+    "tts_convbn_create", "tts_convbn_destroy", "tts_convbn_set_weights", "tts_convbn_reserve_floats",
+    "tts_convbn_forward", "tts_convbn_backward",
     "tts_last_error", "tts_version",
 )
 
@@ -200,6 +202,15 @@ def _declare(lib):
     lib.tts_lstm_reserve_floats.restype = ctypes.c_int64
     lib.tts_lstm_forward.argtypes = [vp, vp, I32P, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp]
     lib.tts_lstm_backward.argtypes = [vp, vp, I32P, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, PP, PP, PP, PP, vp]
+    lib.tts_convbn_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
+    lib.tts_convbn_destroy.argtypes = [vp]
+    lib.tts_convbn_destroy.restype = None
+    lib.tts_convbn_set_weights.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.tts_convbn_reserve_floats.argtypes = [vp, ctypes.c_int, ctypes.c_int]
+    lib.tts_convbn_reserve_floats.restype = ctypes.c_int64
+    lib.tts_convbn_forward.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_float, vp, vp, D, D,
+                                       ctypes.c_int, vp, vp, vp]
+    lib.tts_convbn_backward.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.tts_last_error.restype = ctypes.c_char_p
     lib.tts_version.restype = ctypes.c_char_p
     for name in EXPORTS:

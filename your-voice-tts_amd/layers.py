@@ -19,6 +19,10 @@ when the parameters' version counters or addresses have changed since the last c
 covers ``optimizer.step()``, ``load_state_dict`` and ``.to()``.
 
 Without a GPU a call raises the package's "no GPU" RuntimeError; there is no CPU fallback.
+
+``ConvBNBlock`` is the reference's conv-BN block (layers/tacotron2.py:9-27) with the same ``net`` Sequential, hence
+the same state dict, and ``tts_convbn_forward`` / ``tts_convbn_backward`` (csrc/convbn_train.hip) as its forward and
+backward; ``use_device_convs(model)`` swaps it into ``encoder.convolutions`` and ``postnet.convolutions``.
 """
 from __future__ import annotations
 
@@ -259,4 +263,224 @@ def use_device_lstm(model):
     new.to(p.device)
     new.train(old.training)
     model.encoder.lstm = new
+    return model
+
+
+# ---------------------------------------------------------------------- the conv-BN block
+_ACTS = {None: 0, "relu": 1, "tanh": 2}
+
+
+class _ConvBNFunction(torch.autograd.Function):
+    """forward(x [B, Cin, T], module, mask, *parameters) -> out.  The parameters ride along so that autograd asks for
+    their gradients; the kernels read the module's repacked copies."""
+
+    @staticmethod
+    def forward(ctx, x, module, mask, *params):
+        out, reserve = module._run_forward(x, mask, True)
+        ctx.save_for_backward(x, reserve, mask)
+        ctx.module = module
+        ctx.versions = module._key()
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        x, reserve, mask = ctx.saved_tensors
+        m = ctx.module
+        if m._key() != ctx.versions:
+            raise RuntimeError("layers.ConvBNBlock: the parameters were modified between this forward and its backward")
+        need = ctx.needs_input_grad
+        grads = m._run_backward(x, reserve, mask, grad_out, need[0], need[3:])
+        return (grads[0], None, None) + tuple(grads[1:])
+
+
+class ConvBNBlock(nn.Module):
+    """The reference's ``ConvBNBlock`` (layers/tacotron2.py:9-27) on the device: ``self.net`` is built exactly as
+    there (``nn.Sequential(Conv1d(k=5, padding=2), BatchNorm1d, [ReLU | Tanh], Dropout(0.5))``), so parameter and
+    buffer names, shapes and initialisation are the reference's and state dicts load both ways; only ``forward``
+    is replaced, by ``tts_convbn_forward`` / ``tts_convbn_backward`` (csrc/convbn_train.hip).
+
+    ``forward(x, mask=None)``: ``x`` is ``[B, Cin, T]`` float32 on the device, any strided view (copied once where
+    it is not contiguous; same bits).  ``mask`` (uint8 or bool ``[B, Cout, T]``, 1 = keep) fixes the dropout mask;
+    without it the mask is drawn on the device from torch's generator (``torch.manual_seed`` governs it).
+    ``last_mask`` is the mask that was used (None in ``eval()``), the scale is ``1 / (1 - net[-1].p)``.  In training
+    mode the batch statistics normalise and the kernel updates ``running_mean`` / ``running_var`` in place
+    (``num_batches_tracked += 1``); in ``eval()`` the running statistics normalise, there is no dropout and ``mask``
+    is ignored.  With grad mode off, or when nothing requires grad, no reserve is kept (``last_reserve_floats``
+    is 0) and the output has the same bits.  The weights are repacked when the parameters' version counters or
+    addresses have changed (``repacks`` counts).  Without a GPU a call raises the package's "no GPU" RuntimeError;
+    there is no CPU path."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, nonlinear=None):
+        super().__init__()
+        for ok, what in ((kernel_size == 5, "a kernel_size other than 5"),
+                         (nonlinear in _ACTS, f"nonlinear={nonlinear!r}"),
+                         (in_channels > 0 and in_channels % 16 == 0, "in_channels that are no multiple of 16"),
+                         (out_channels > 0 and out_channels % 16 == 0, "out_channels that are no multiple of 16")):
+            if not ok:
+                raise NotImplementedError(f"layers.ConvBNBlock does not implement {what}")
+        padding = (kernel_size - 1) // 2
+        conv1d = nn.Conv1d(in_channels, out_channels, kernel_size, padding=padding)
+        norm = nn.BatchNorm1d(out_channels)
+        dropout = nn.Dropout(p=0.5)
+        if nonlinear == "relu":
+            self.net = nn.Sequential(conv1d, norm, nn.ReLU(), dropout)
+        elif nonlinear == "tanh":
+            self.net = nn.Sequential(conv1d, norm, nn.Tanh(), dropout)
+        else:
+            self.net = nn.Sequential(conv1d, norm, dropout)
+        self.in_channels, self.out_channels, self.kernel_size, self.nonlinear = in_channels, out_channels, 5, nonlinear
+        self._h = None
+        self._packed_key = None
+        self.repacks = 0
+        self.last_reserve_floats = 0
+        self.last_mask = None
+
+    def __del__(self):
+        try:
+            if self._h is not None:
+                self._h[0].tts_convbn_destroy(self._h[1])
+        except Exception:
+            pass
+
+    # ------------------------------------------------------------------ the handle and its weights
+    def _params(self):
+        conv, norm = self.net[0], self.net[1]
+        return [conv.weight, conv.bias, norm.weight, norm.bias]
+
+    def _key(self):
+        return tuple((p.data_ptr(), p._version) for p in self._params())
+
+    def _handle(self):
+        lib = _native.lib()  # raises without a GPU / library: no CPU fallback
+        if self._h is None:
+            h = ctypes.c_void_p()
+            _native.check(lib.tts_convbn_create(self.in_channels, self.out_channels, self.kernel_size,
+                                                _ACTS[self.nonlinear], ctypes.byref(h)), "tts_convbn_create")
+            self._h = (lib, h)
+        return self._h
+
+    def _sync_weights(self):
+        lib, h = self._handle()
+        key = self._key()
+        if key == self._packed_key:
+            return
+        ps = self._params()
+        for p in ps:
+            if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+                raise ValueError("layers.ConvBNBlock: parameters must be contiguous CUDA float32 tensors")
+        _native.check(lib.tts_convbn_set_weights(h, *[_ptr(p) for p in ps], _native.stream_handle()),
+                      "tts_convbn_set_weights")
+        self._packed_key = key
+        self.repacks += 1
+
+    # ------------------------------------------------------------------ the two calls
+    def _run_forward(self, x, mask, want_reserve):
+        lib, h = self._handle()
+        self._sync_weights()
+        norm, drop = self.net[1], self.net[-1]
+        for buf in (norm.running_mean, norm.running_var):
+            if not buf.is_cuda or buf.dtype != torch.float32 or not buf.is_contiguous():
+                raise ValueError("layers.ConvBNBlock: the running buffers must be contiguous CUDA float32 tensors")
+        B, _, T = x.shape
+        x = x.detach().contiguous()
+        out = torch.empty(B, self.out_channels, T, dtype=torch.float32, device=x.device)
+        reserve = None
+        if want_reserve and self.training:
+            reserve = torch.empty(lib.tts_convbn_reserve_floats(h, B, T), dtype=torch.float32, device=x.device)
+        self.last_reserve_floats = 0 if reserve is None else reserve.numel()
+        _native.check(lib.tts_convbn_forward(h, _ptr(x), B, T, _ptr(mask), 1.0 / (1.0 - drop.p),
+                                             _ptr(norm.running_mean), _ptr(norm.running_var), float(norm.momentum),
+                                             float(norm.eps), int(self.training), _ptr(out), _ptr(reserve),
+                                             _native.stream_handle()), "tts_convbn_forward")
+        if self.training:
+            norm.num_batches_tracked += 1
+        return out, reserve
+
+    def _run_backward(self, x, reserve, mask, grad_out, need_x, need_params):
+        lib, h = self._handle()
+        B, _, T = x.shape
+        x = x.detach().contiguous()
+        grad_out = grad_out.contiguous()
+        grad_x = torch.empty_like(x) if need_x else None
+        gp = [torch.empty_like(p) if need else None for p, need in zip(self._params(), need_params)]
+        _native.check(lib.tts_convbn_backward(h, _ptr(x), B, T, _ptr(reserve), _ptr(mask), _ptr(grad_out), _ptr(grad_x),
+                                              *[_ptr(g) for g in gp], _native.stream_handle()), "tts_convbn_backward")
+        return [grad_x] + gp
+
+    def forward(self, x, mask=None):
+        norm, drop = self.net[1], self.net[-1]
+        if norm.momentum is None or not norm.track_running_stats:
+            raise NotImplementedError("layers.ConvBNBlock implements neither momentum=None nor "
+                                      "track_running_stats=False")
+        if x.dim() != 3 or x.shape[1] != self.in_channels:
+            raise ValueError(f"expected input [B, {self.in_channels}, T], got {tuple(x.shape)}")
+        if not x.is_cuda:
+            _native.lib()  # the "no GPU" error where there is none
+            raise RuntimeError("layers.ConvBNBlock: the input must be a CUDA tensor (there is no CPU path)")
+        if x.dtype != torch.float32:
+            raise ValueError(f"layers.ConvBNBlock: the input must be float32, got {x.dtype}")
+        B, _, T = x.shape
+        if B < 1 or T < 1:
+            raise ValueError(f"layers.ConvBNBlock: an empty input {tuple(x.shape)}")
+        shape = (B, self.out_channels, T)
+        if not self.training:
+            self.last_mask = None
+            return self._run_forward(x, None, False)[0]
+        if B * T == 1:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+        if not 0.0 <= drop.p < 1.0:
+            raise NotImplementedError("layers.ConvBNBlock needs a dropout probability in [0, 1)")
+        if mask is None:
+            mask = (torch.rand(shape, device=x.device) >= drop.p).to(torch.uint8)
+        else:
+            if tuple(mask.shape) != shape or mask.dtype not in (torch.uint8, torch.bool):
+                raise ValueError(f"expected a uint8 or bool mask of shape {shape}, got {mask.dtype} {tuple(mask.shape)}")
+            mask = mask.to(x.device, torch.uint8).contiguous()
+        self.last_mask = mask
+        params = self._params()
+        if not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))):
+            return self._run_forward(x, mask, False)[0]
+        return _ConvBNFunction.apply(x, self, mask, *params)
+
+
+def _conv_block_shape(block):
+    """(conv, norm, nonlinear, dropout) when ``block.net`` is the reference's Sequential of Conv1d, BatchNorm1d,
+    [ReLU | Tanh], Dropout; else None."""
+    net = getattr(block, "net", None)
+    if not isinstance(net, nn.Sequential) or len(net) not in (3, 4):
+        return None
+    if not (isinstance(net[0], nn.Conv1d) and isinstance(net[1], nn.BatchNorm1d) and isinstance(net[-1], nn.Dropout)):
+        return None
+    nonlinear = None
+    if len(net) == 4:
+        nonlinear = "relu" if isinstance(net[2], nn.ReLU) else "tanh" if isinstance(net[2], nn.Tanh) else False
+        if nonlinear is False:
+            return None
+    return net[0], net[1], nonlinear, net[-1]
+
+
+def use_device_convs(model):
+    """Swap every conv-BN block of ``model.encoder.convolutions`` and ``model.postnet.convolutions`` (whichever
+    exist; layers/tacotron2.py:52-55, :30-45) for a ``layers.ConvBNBlock`` that carries the same parameters and
+    buffers on the same device in the same training mode; returns the model.  A block is recognised by its
+    structure (a ``.net`` Sequential of Conv1d, BatchNorm1d, [ReLU | Tanh], Dropout).  Calling it again changes
+    nothing.  Build the optimizer afterwards: the parameters are new tensors.  Measured against torch's own
+    blocks on an MI355X: profiles/convbn_train.json ("timing")."""
+    for part in ("encoder", "postnet"):
+        convs = getattr(getattr(model, part, None), "convolutions", None)
+        if convs is None:
+            continue
+        for i, old in enumerate(convs):
+            found = None if isinstance(old, ConvBNBlock) else _conv_block_shape(old)
+            if found is None:
+                continue
+            conv, norm, nonlinear, drop = found
+            new = ConvBNBlock(conv.in_channels, conv.out_channels, conv.kernel_size[0], nonlinear)
+            new.load_state_dict(old.state_dict())
+            new.net[1].eps, new.net[1].momentum = norm.eps, norm.momentum
+            new.net[-1].p = drop.p
+            new.to(conv.weight.device)
+            new.train(old.training)
+            convs[i] = new
     return model

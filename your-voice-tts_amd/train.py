@@ -7,7 +7,9 @@ reports for the same outputs), ``loss.backward()``, and the update: ``optim.Adam
 is the package's, ``weight_decay(); check_update(); optimizer.step()`` otherwise.  Forward and backward of the
 *model* stay the caller's torch, except for the encoder's LSTM once ``layers.use_device_lstm(model)`` has swapped
 it for ``layers.LSTM`` (``tts_lstm_forward`` / ``tts_lstm_backward``; build the optimizer after the swap); the
-criteria's backward is ``tts_loss_backward``.
+criteria's backward is ``tts_loss_backward``.  ``layers.use_device_convs(model)`` does the same for every conv-BN
+block of ``encoder.convolutions`` and ``postnet.convolutions`` (``layers.ConvBNBlock``: ``tts_convbn_forward`` /
+``tts_convbn_backward``), after which the whole encoder and the whole Postnet train on the device.
 
 Not part of it: the epoch loop, the logging, checkpoints, ``reduce_tensor`` across ranks and the diagnostic
 audio of train.py:171-260.
