@@ -794,6 +794,115 @@ tts_status tts_convbn_backward(tts_convbn* h, const float* x, int B, int T, cons
                                const float* grad_out, float* grad_x, float* grad_W, float* grad_bias, float* grad_gamma,
                                float* grad_beta, void* stream);
 
+/* ---------------------------------------------------------------- trainable Tacotron2 decoder (decoder_train.hip)
+ * The reference's Decoder (layers/tacotron2.py:97-247) as Decoder.forward runs it teacher-forced, with its whole
+ * backward through time: prenet ("original"), attention LSTM cell, attention (no location term, no transition
+ * agent; "sigmoid" or "softmax" norm, forward attention with u = 0.5 or none), decoder LSTM cell, projection,
+ * stopnet (separate: reads its input detached; else its input gradient joins).  Every product is an exact fp32
+ * MFMA chain, every reduction has a fixed order and nothing is accumulated with atomics: the same operands and
+ * masks give the same bits.  Plain launches on the caller's stream; no call waits for the stream or copies to or
+ * from the host; a workspace that has to grow is freed and allocated again, which waits for the device that
+ * once.  The handle owns the repacked weights (transposed copies included) and the workspaces; all calls on one
+ * handle must be ordered on one stream.  The reserve belongs to the caller, so several forwards may be
+ * outstanding before their backwards.  [dev] tensors are contiguous fp32 with 4-byte alignment, the reserve
+ * 16-byte.
+ *
+ * Shapes: B sentences, L text positions, T decoder steps (= mel frames / r), MR = mel * r.
+ * Dropout masks are operands: uint8, 1 = keep, step-major ([T][B][...]: step t of sentence b is row t * B + b). */
+typedef struct tts_dectrain tts_dectrain;
+
+/* The reference's parameter tensors by name, [dev], in the reference's layouts. */
+typedef struct {
+    const float* prenet_w1; /* prenet.layers.0.linear_layer.weight            [prenet][MR] */
+    const float* prenet_w2; /* prenet.layers.1.linear_layer.weight            [prenet][prenet] */
+    const float* att_w_ih;  /* attention_rnn.weight_ih                        [4 rnn][prenet + enc] */
+    const float* att_w_hh;  /* attention_rnn.weight_hh                        [4 rnn][rnn] */
+    const float* att_b_ih;  /* attention_rnn.bias_ih                          [4 rnn] */
+    const float* att_b_hh;  /* attention_rnn.bias_hh                          [4 rnn] */
+    const float* query_w;   /* attention_layer.query_layer.linear_layer.weight  [att][rnn] */
+    const float* inputs_w;  /* attention_layer.inputs_layer.linear_layer.weight [att][enc] */
+    const float* v_w;       /* attention_layer.v.linear_layer.weight          [1][att] */
+    const float* v_b;       /* attention_layer.v.linear_layer.bias            [1] */
+    const float* dec_w_ih;  /* decoder_rnn.weight_ih                          [4 rnn][rnn + enc] */
+    const float* dec_w_hh;  /* decoder_rnn.weight_hh                          [4 rnn][rnn] */
+    const float* dec_b_ih;  /* decoder_rnn.bias_ih                            [4 rnn] */
+    const float* dec_b_hh;  /* decoder_rnn.bias_hh                            [4 rnn] */
+    const float* proj_w;    /* linear_projection.linear_layer.weight          [MR][rnn + enc] */
+    const float* proj_b;    /* linear_projection.linear_layer.bias            [MR] */
+    const float* stop_w;    /* stopnet.1.linear_layer.weight                  [1][rnn + MR] */
+    const float* stop_b;    /* stopnet.1.linear_layer.bias                    [1] */
+    const float* att_init;  /* attention_rnn_init.weight                      [1][rnn] */
+    const float* go_init;   /* go_frame_init.weight                           [1][MR] */
+    const float* dec_init;  /* decoder_rnn_inits.weight                       [1][rnn] */
+} tts_dectrain_weights;
+
+/* The same table for the gradients, [dev] out in the parameters' layouts; any entry may be NULL (skipped). */
+typedef struct {
+    float *prenet_w1, *prenet_w2, *att_w_ih, *att_w_hh, *att_b_ih, *att_b_hh, *query_w, *inputs_w, *v_w, *v_b, *dec_w_ih,
+        *dec_w_hh, *dec_b_ih, *dec_b_hh, *proj_w, *proj_b, *stop_w, *stop_b, *att_init, *go_init, *dec_init;
+} tts_dectrain_grads;
+
+/* The four groups of dropout masks of a training forward and their scales 1 / (1 - p). */
+typedef struct {
+    const uint8_t* prenet1; /* [T][B][prenet] after the first prenet layer  (prenet_dropout only) */
+    const uint8_t* prenet2; /* [T][B][prenet] after the second */
+    const uint8_t* att_h;   /* [T][B][rnn] on the attention LSTM's h */
+    const uint8_t* att_c;   /* [T][B][rnn] on its cell state: the dropped tensors are the carried state */
+    const uint8_t* dec_h;   /* [T][B][rnn] decoder LSTM */
+    const uint8_t* dec_c;   /* [T][B][rnn] */
+    const uint8_t* stop;    /* [T][B][rnn + MR] on the stopnet's input [h_dec | decoder_output] */
+    float scale_prenet, scale_rnn, scale_stop;
+} tts_dectrain_masks;
+
+/* norm: 0 "sigmoid", 1 "softmax" (else INVALID).  UNSUPPORTED unless enc, prenet, rnn and att are positive
+ * multiples of 16 and mel_r is positive. */
+tts_status tts_dectrain_create(int enc, int prenet, int rnn, int att, int mel_r, int norm, int forward_attn,
+                               int prenet_dropout, int separate_stopnet, tts_dectrain** out);
+void tts_dectrain_destroy(tts_dectrain* h);
+
+/* Repacks the parameters on the stream into the orders the kernels read (gate-interleaved rows for the two
+ * cells' forward, transposed copies for the backward, mel * r padded to 16); call it again whenever the
+ * parameters have changed.  INVALID: a null entry. */
+tts_status tts_dectrain_set_weights(tts_dectrain* h, const tts_dectrain_weights* w, void* stream);
+
+/* Floats of the reserve a forward of this shape fills: both cells' h of every step (and the initial rows), the
+ * contexts, alpha, the queries, both cells' activated gates and cell states, the prenet's two outputs, the
+ * frames, decoder_output, the processed memory and the inputs with +0.0 on masked rows.  0 for a null handle or
+ * a non-positive B, L or T. */
+int64_t tts_dectrain_reserve_floats(const tts_dectrain* h, int B, int L, int T);
+
+/* Decoder.forward(inputs, memories, mask) (layers/tacotron2.py:227-247).
+ *   inputs     [dev]  [B][L][enc]; a row with mask == 0 never reaches a product (selected away)
+ *   memories   [dev]  [B][T * r][mel] the teacher's frames; the last group of r frames is not read
+ *   mask       [dev]  uint8 [B][L], 1 = valid, or NULL (all valid).  The host never reads it; every sentence needs
+ *                     one valid position (not checked: undefined otherwise, as in the reference)
+ *   training   1: the masks of m drop (all but prenet1 / prenet2 required; those with prenet_dropout); 0: m is not
+ *              read and nothing is dropped
+ *   out        [dev]  [B][T][MR] decoder_output (the reference's outputs is its view [B][T * r][mel] transposed)
+ *   stop       [dev]  [B][T];  alignments [dev] [B][T][L]
+ *   reserve    [dev]  tts_dectrain_reserve_floats(h, B, L, T) floats, or NULL (no backward will follow: the handle's
+ *                     own block is used and the outputs are bitwise the same)
+ * INVALID before any launch: a null handle or tensor; weights not set; B, L or T <= 0; L > 2048 or
+ * 4 * ceil16(L) + enc + 512 floats above the 64 KB of LDS the attention kernels may ask for; training
+ * without its masks or with a scale <= 0; a misaligned reserve.  10 launches, 4 per step, 3. */
+tts_status tts_dectrain_forward(tts_dectrain* h, const float* inputs, const float* memories, const uint8_t* mask, int B,
+                                int L, int T, int training, const tts_dectrain_masks* m, float* out, float* stop,
+                                float* alignments, float* reserve, void* stream);
+
+/* The backward of that training forward.
+ *   mask, B, L, T, m  as the forward had them; reserve: what it wrote
+ *   grad_out   [dev]  [B][T][MR] or NULL (zeros);  grad_stop [dev] [B][T] or NULL (zeros); one of them is required.
+ *              With a separate stopnet grad_stop reaches only stop_w and stop_b.
+ *   grad_inputs [dev] [B][L][enc] (through the contexts and the processed memory; +0.0 on masked rows);
+ *   grad_memories [dev] [B][T * r][mel] (+0.0 on the last group);  g: the parameters' gradients
+ * Gradients are WRITTEN, not accumulated.  Any gradient pointer may be NULL; that product is skipped, and when
+ * only stop_w / stop_b are asked for the walk back through time is skipped altogether.  The weights are those of
+ * the last tts_dectrain_set_weights: they must be the forward's.  INVALID before any launch: as the forward; a
+ * null reserve, m, g or mask group; neither grad_out nor grad_stop. */
+tts_status tts_dectrain_backward(tts_dectrain* h, const uint8_t* mask, int B, int L, int T, const tts_dectrain_masks* m,
+                                 const float* reserve, const float* grad_out, const float* grad_stop, float* grad_inputs,
+                                 float* grad_memories, const tts_dectrain_grads* g, void* stream);
+
 const char* tts_last_error(void);
 const char* tts_version(void);
 

@@ -51,6 +51,8 @@ EXPORTS = (
     "tts_lstm_backward",
     "tts_convbn_create", "tts_convbn_destroy", "tts_convbn_set_weights", "tts_convbn_reserve_floats",
     "tts_convbn_forward", "tts_convbn_backward",
+    "tts_dectrain_create", "tts_dectrain_destroy", "tts_dectrain_set_weights", "tts_dectrain_reserve_floats",
+    "tts_dectrain_forward", "tts_dectrain_backward",
     "tts_last_error", "tts_version",
 )
 
@@ -82,6 +84,28 @@ class AudioConfig(ctypes.Structure):
                 ("ref_level_db", ctypes.c_float), ("power", ctypes.c_float),
                 ("max_norm", ctypes.c_float), ("preemphasis", ctypes.c_double),
                 ("signal_norm", ctypes.c_int), ("symmetric_norm", ctypes.c_int), ("clip_norm", ctypes.c_int)]
+
+
+# tts_dectrain_weights / tts_dectrain_grads: the reference Decoder's parameters, state-dict name -> field order
+DECTRAIN_PARAMS = (
+    "prenet.layers.0.linear_layer.weight", "prenet.layers.1.linear_layer.weight",
+    "attention_rnn.weight_ih", "attention_rnn.weight_hh", "attention_rnn.bias_ih", "attention_rnn.bias_hh",
+    "attention_layer.query_layer.linear_layer.weight", "attention_layer.inputs_layer.linear_layer.weight",
+    "attention_layer.v.linear_layer.weight", "attention_layer.v.linear_layer.bias",
+    "decoder_rnn.weight_ih", "decoder_rnn.weight_hh", "decoder_rnn.bias_ih", "decoder_rnn.bias_hh",
+    "linear_projection.linear_layer.weight", "linear_projection.linear_layer.bias",
+    "stopnet.1.linear_layer.weight", "stopnet.1.linear_layer.bias",
+    "attention_rnn_init.weight", "go_frame_init.weight", "decoder_rnn_inits.weight")
+DECTRAIN_MASKS = ("prenet1", "prenet2", "att_h", "att_c", "dec_h", "dec_c", "stop")
+
+
+class DectrainTensors(ctypes.Structure):  # tts_dectrain_weights, tts_dectrain_grads
+    _fields_ = [(f"p{i}", ctypes.c_void_p) for i in range(len(DECTRAIN_PARAMS))]
+
+
+class DectrainMasks(ctypes.Structure):  # tts_dectrain_masks
+    _fields_ = [(n, ctypes.c_void_p) for n in DECTRAIN_MASKS] + [
+        ("scale_prenet", ctypes.c_float), ("scale_rnn", ctypes.c_float), ("scale_stop", ctypes.c_float)]
 
 
 _lib = None
@@ -211,6 +235,17 @@ def _declare(lib):
     lib.tts_convbn_forward.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_float, vp, vp, D, D,
                                        ctypes.c_int, vp, vp, vp]
     lib.tts_convbn_backward.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    ci = ctypes.c_int
+    lib.tts_dectrain_create.argtypes = [ci] * 9 + [ctypes.POINTER(vp)]
+    lib.tts_dectrain_destroy.argtypes = [vp]
+    lib.tts_dectrain_destroy.restype = None
+    lib.tts_dectrain_set_weights.argtypes = [vp, ctypes.POINTER(DectrainTensors), vp]
+    lib.tts_dectrain_reserve_floats.argtypes = [vp, ci, ci, ci]
+    lib.tts_dectrain_reserve_floats.restype = ctypes.c_int64
+    lib.tts_dectrain_forward.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ctypes.POINTER(DectrainMasks), vp, vp, vp, vp,
+                                         vp]
+    lib.tts_dectrain_backward.argtypes = [vp, vp, ci, ci, ci, ctypes.POINTER(DectrainMasks), vp, vp, vp, vp, vp,
+                                          ctypes.POINTER(DectrainTensors), vp]
     lib.tts_last_error.restype = ctypes.c_char_p
     lib.tts_version.restype = ctypes.c_char_p
     for name in EXPORTS:

@@ -484,3 +484,345 @@ def use_device_convs(model):
             new.train(old.training)
             convs[i] = new
     return model
+
+
+# ---------------------------------------------------------------------- the decoder
+_P_PRENET, _NORMS = 0.5, {"sigmoid": 0, "softmax": 1}
+_MASK_GROUPS = ("prenet", "att", "dec", "stop")
+
+
+class _Linear(nn.Module):
+    """The reference's ``Linear`` (layers/common_layers.py:8-25): ``linear_layer`` with Xavier-uniform weights."""
+
+    def __init__(self, in_features, out_features, bias=True, init_gain="linear"):
+        super().__init__()
+        self.linear_layer = nn.Linear(in_features, out_features, bias=bias)
+        nn.init.xavier_uniform_(self.linear_layer.weight, gain=nn.init.calculate_gain(init_gain))
+
+    def forward(self, x):
+        return self.linear_layer(x)
+
+
+def _decoder_unsupported(prenet_type, trans_agent, location_attn):
+    for bad, what in ((location_attn, "location_attn"), (trans_agent, "trans_agent"),
+                      (prenet_type != "original", f"prenet_type={prenet_type!r}")):
+        if bad:
+            raise NotImplementedError(f"layers.Decoder does not implement {what}")
+
+
+class _DecoderFunction(torch.autograd.Function):
+    """forward(inputs, memories, module, mask, masks, *parameters) -> (out [B, T, MR], stop, alignments, reserve).
+    ``alignments`` is not differentiable.  With a separate stopnet ``stop`` is not differentiable here either: the
+    stop tokens join autograd through ``_StopFunction``, a node of its own, so a second backward through them works
+    after this one; otherwise their gradient arrives here together with that of ``out``."""
+
+    @staticmethod
+    def forward(ctx, inputs, memories, module, mask, masks, *params):
+        out, stop, align, reserve = module._run_forward(inputs, memories, mask, masks, True)
+        ctx.save_for_backward(reserve, mask, *[masks[k] for k in _MASK_GROUPS])
+        ctx.module, ctx.shape = module, (inputs.shape[0], inputs.shape[1], stop.shape[1])
+        ctx.versions = module._key()
+        if module.separate_stopnet:
+            ctx.mark_non_differentiable(stop, align, reserve)
+        else:
+            ctx.mark_non_differentiable(align, reserve)
+        return out, stop, align, reserve
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out, grad_stop, _ga, _gr):
+        reserve, mask, *mk = ctx.saved_tensors
+        m = ctx.module
+        if m._key() != ctx.versions:
+            raise RuntimeError("layers.Decoder: the parameters were modified between this forward and its backward")
+        need, need_params = ctx.needs_input_grad, list(ctx.needs_input_grad[5:])
+        if m.separate_stopnet:  # the stopnet's weight and bias (positions 16, 17) belong to _StopFunction
+            grad_stop = None
+            need_params[16] = need_params[17] = False
+        grads = m._run_backward(ctx.shape, mask, dict(zip(_MASK_GROUPS, mk)), reserve, grad_out, grad_stop, need[0],
+                                need[1], need_params)
+        return (grads[0], grads[1], None, None, None) + tuple(grads[2:])
+
+
+class _StopFunction(torch.autograd.Function):
+    """forward(stop_raw, module, mask, masks, reserve, shape, *parameters) -> the stop tokens of a separate stopnet:
+    only its own weight and bias receive gradients (its input is detached), without a walk back through time."""
+
+    @staticmethod
+    def forward(ctx, stop_raw, module, mask, masks, reserve, shape, *params):
+        ctx.save_for_backward(reserve, mask, *[masks[k] for k in _MASK_GROUPS])
+        ctx.module, ctx.shape = module, shape
+        return stop_raw.clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_stop):
+        reserve, mask, *mk = ctx.saved_tensors
+        m = ctx.module
+        # (no stale-parameter check: these two gradients read the reserve alone, so train_batch may step the main
+        #  optimizer between the two backwards, as the reference does)
+        need = [n and i in (16, 17) for i, n in enumerate(ctx.needs_input_grad[6:])]
+        grads = m._run_backward(ctx.shape, mask, dict(zip(_MASK_GROUPS, mk)), reserve, None, grad_stop, False, False, need)
+        return (None,) * 6 + tuple(grads[2:])
+
+
+class Decoder(nn.Module):
+    """The reference's ``Decoder`` (layers/tacotron2.py:97-247) with its teacher-forced ``forward`` and the whole
+    backward through time on the device (``tts_dectrain_forward`` / ``tts_dectrain_backward``,
+    csrc/decoder_train.hip).  The submodules are built under the reference's names, so ``state_dict()`` keys,
+    shapes and initialisation are the reference's and state dicts load both ways.
+
+    ``forward(inputs [B, L, in_features], memories [B, T * r, mel], mask [B, L] or None, masks=None)`` returns the
+    reference's ``(outputs [B, mel, T * r], stop_tokens [B, T], alignments [B, T, L])``; ``alignments`` is for logging
+    and not differentiable.  ``masks`` fixes the dropout masks: a dict of the four groups, uint8 with 1 = keep,
+    ``prenet [2, T, B, prenet]`` (p = 0.5; absent or ignored without ``prenet_dropout``), ``att [2, T, B, rnn]`` (h, c
+    of the attention LSTM, p = 0.1), ``dec [2, T, B, rnn]``, ``stop [T, B, rnn + mel * r]`` (p = ``stopnet[0].p``); without
+    it they are drawn on the device from torch's generator.  ``last_masks`` holds what was used (None in ``eval()``).
+    A masked row of ``inputs`` never reaches a product; ``grad_inputs`` is +0.0 there.
+
+    ``location_attn``, ``trans_agent`` and ``prenet_type="bn"`` raise ``NotImplementedError``.  ``attn_win`` and
+    ``forward_attn_mask`` act only in ``eval()``: accepted and ignored in ``train()``; an ``eval()`` forward with either
+    set raises.  ``inference*`` are not part of this module: use the package's ``Tacotron2.inference``.
+
+    With grad mode off, or when nothing requires grad, no reserve is kept (``last_reserve_floats`` is 0) and the
+    outputs have the same bits.  In ``eval()`` the forward runs without dropout and its outputs do NOT join autograd,
+    even with grad mode on (unlike the reference's ``Decoder``, whose ``eval()`` forward is differentiable): the backward
+    exists for training forwards only, as for ``layers.LSTM``.  The weights are repacked when the parameters' version counters or addresses have
+    changed (``repacks`` counts).  Without a GPU a call raises the package's "no GPU" RuntimeError; there is no CPU
+    path."""
+
+    def __init__(self, in_features, inputs_dim, r, attn_win, attn_norm, prenet_type, prenet_dropout, forward_attn,
+                 trans_agent, forward_attn_mask, location_attn, separate_stopnet, prenet_dim=256, rnn_dim=1024,
+                 attention_dim=128):
+        super().__init__()
+        _decoder_unsupported(prenet_type, trans_agent, location_attn)
+        if attn_norm not in _NORMS:
+            raise RuntimeError("Unknown value for attention norm type")
+        for v, what in ((in_features, "in_features"), (prenet_dim, "prenet_dim"), (rnn_dim, "rnn_dim"),
+                        (attention_dim, "attention_dim")):
+            if v <= 0 or v % 16:
+                raise NotImplementedError(f"layers.Decoder does not implement a {what} that is no multiple of 16")
+        self.mel_channels, self.r, self.encoder_embedding_dim = inputs_dim, r, in_features
+        self.separate_stopnet = separate_stopnet
+        self.attention_rnn_dim = self.decoder_rnn_dim = rnn_dim
+        self.prenet_dim, self.attention_dim = prenet_dim, attention_dim
+        self.max_decoder_steps, self.gate_threshold = 1000, 0.5
+        self.p_attention_dropout = self.p_decoder_dropout = 0.1
+        MR = inputs_dim * r
+        self.prenet = nn.Module()
+        self.prenet.prenet_type, self.prenet.prenet_dropout = prenet_type, prenet_dropout
+        self.prenet.layers = nn.ModuleList([_Linear(MR, prenet_dim, bias=False), _Linear(prenet_dim, prenet_dim, bias=False)])
+        self.attention_rnn = nn.LSTMCell(prenet_dim + in_features, rnn_dim)
+        att = nn.Module()
+        att.query_layer = _Linear(rnn_dim, attention_dim, bias=False, init_gain="tanh")
+        att.inputs_layer = _Linear(in_features, attention_dim, bias=False, init_gain="tanh")
+        att.v = _Linear(attention_dim, 1, bias=True)
+        att.windowing, att.norm, att.forward_attn, att.trans_agent = attn_win, attn_norm, forward_attn, trans_agent
+        att.forward_attn_mask, att.location_attention = forward_attn_mask, location_attn
+        self.attention_layer = att
+        self.decoder_rnn = nn.LSTMCell(rnn_dim + in_features, rnn_dim, 1)
+        self.linear_projection = _Linear(rnn_dim + in_features, MR)
+        self.stopnet = nn.Sequential(nn.Dropout(0.1), _Linear(rnn_dim + MR, 1, bias=True, init_gain="sigmoid"))
+        self.attention_rnn_init = nn.Embedding(1, rnn_dim)
+        self.go_frame_init = nn.Embedding(1, MR)
+        self.decoder_rnn_inits = nn.Embedding(1, rnn_dim)
+        self.memory_truncated = None
+        self._h = None
+        self._packed_key = None
+        self.repacks = 0
+        self.last_reserve_floats = 0
+        self.last_masks = None
+
+    def __del__(self):
+        try:
+            if self._h is not None:
+                self._h[0].tts_dectrain_destroy(self._h[1])
+        except Exception:
+            pass
+
+    def inference(self, *args, **kwargs):
+        raise NotImplementedError("layers.Decoder trains; synthesis is the package's Tacotron2.inference")
+
+    inference_truncated = inference_step = inference
+
+    # ------------------------------------------------------------------ the handle and its weights
+    def _params(self):
+        named = dict(self.named_parameters())
+        return [named[n] for n in _native.DECTRAIN_PARAMS]
+
+    def _key(self):
+        return tuple((p.data_ptr(), p._version) for p in self._params())
+
+    def _handle(self):
+        lib = _native.lib()  # raises without a GPU / library: no CPU fallback
+        if self._h is None:
+            h = ctypes.c_void_p()
+            a = self.attention_layer
+            _native.check(lib.tts_dectrain_create(self.encoder_embedding_dim, self.prenet_dim, self.attention_rnn_dim,
+                                                  self.attention_dim, self.mel_channels * self.r, _NORMS[a.norm],
+                                                  int(bool(a.forward_attn)), int(bool(self.prenet.prenet_dropout)),
+                                                  int(bool(self.separate_stopnet)), ctypes.byref(h)),
+                          "tts_dectrain_create")
+            self._h = (lib, h)
+        return self._h
+
+    def _sync_weights(self):
+        lib, h = self._handle()
+        key = self._key()
+        if key == self._packed_key:
+            return
+        ps = self._params()
+        for p in ps:
+            if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+                raise ValueError("layers.Decoder: parameters must be contiguous CUDA float32 tensors")
+        table = _native.DectrainTensors(*[p.data_ptr() for p in ps])
+        _native.check(lib.tts_dectrain_set_weights(h, ctypes.byref(table), _native.stream_handle()),
+                      "tts_dectrain_set_weights")
+        self._packed_key = key
+        self.repacks += 1
+
+    def _mask_table(self, masks):
+        if masks is None:
+            return None
+        pn = masks.get("prenet") if self.prenet.prenet_dropout else None
+        ptr = lambda t: t.data_ptr()
+        return _native.DectrainMasks(ptr(pn[0]) if pn is not None else None, ptr(pn[1]) if pn is not None else None,
+                                     ptr(masks["att"][0]), ptr(masks["att"][1]), ptr(masks["dec"][0]),
+                                     ptr(masks["dec"][1]), ptr(masks["stop"]), 1.0 / (1.0 - _P_PRENET),
+                                     1.0 / (1.0 - self.p_attention_dropout), 1.0 / (1.0 - self.stopnet[0].p))
+
+    # ------------------------------------------------------------------ the two calls
+    def _run_forward(self, inputs, memories, mask, masks, want_reserve):
+        lib, h = self._handle()
+        self._sync_weights()
+        B, L, _ = inputs.shape
+        T, MR = memories.shape[1] // self.r, self.mel_channels * self.r
+        inputs, memories = inputs.detach().contiguous(), memories.detach().contiguous()
+        dev = inputs.device
+        out = torch.empty(B, T, MR, dtype=torch.float32, device=dev)
+        stop = torch.empty(B, T, dtype=torch.float32, device=dev)
+        align = torch.empty(B, T, L, dtype=torch.float32, device=dev)
+        reserve = None
+        if want_reserve:
+            reserve = torch.empty(lib.tts_dectrain_reserve_floats(h, B, L, T), dtype=torch.float32, device=dev)
+        self.last_reserve_floats = 0 if reserve is None else reserve.numel()
+        table = self._mask_table(masks)
+        _native.check(lib.tts_dectrain_forward(h, _ptr(inputs), _ptr(memories), _ptr(mask), B, L, T,
+                                               int(masks is not None), ctypes.byref(table) if table else None,
+                                               _ptr(out), _ptr(stop), _ptr(align), _ptr(reserve),
+                                               _native.stream_handle()), "tts_dectrain_forward")
+        return out, stop, align, reserve
+
+    def _run_backward(self, shape, mask, masks, reserve, grad_out, grad_stop, need_inputs, need_memories, need_params):
+        lib, h = self._handle()
+        B, L, T = shape
+        dev = reserve.device
+        grad_out = grad_out.contiguous() if grad_out is not None else None
+        grad_stop = grad_stop.contiguous() if grad_stop is not None else None
+        g_in = torch.empty(B, L, self.encoder_embedding_dim, dtype=torch.float32, device=dev) if need_inputs else None
+        g_mem = torch.empty(B, T * self.r, self.mel_channels, dtype=torch.float32, device=dev) if need_memories else None
+        gp = [torch.empty_like(p) if need else None for p, need in zip(self._params(), need_params)]
+        table = _native.DectrainTensors(*[g.data_ptr() if g is not None else None for g in gp])
+        mt = self._mask_table(masks)
+        _native.check(lib.tts_dectrain_backward(h, _ptr(mask), B, L, T, ctypes.byref(mt), _ptr(reserve), _ptr(grad_out),
+                                                _ptr(grad_stop), _ptr(g_in), _ptr(g_mem), ctypes.byref(table),
+                                                _native.stream_handle()), "tts_dectrain_backward")
+        return [g_in, g_mem] + gp
+
+    def _draw_masks(self, B, T, device):
+        R, MR = self.attention_rnn_dim, self.mel_channels * self.r
+        shapes = dict(prenet=(2, T, B, self.prenet_dim), att=(2, T, B, R), dec=(2, T, B, R), stop=(T, B, R + MR))
+        p = dict(prenet=_P_PRENET, att=self.p_attention_dropout, dec=self.p_decoder_dropout, stop=self.stopnet[0].p)
+        return {k: (torch.rand(s, device=device) >= p[k]).to(torch.uint8) for k, s in shapes.items()}
+
+    def forward(self, inputs, memories, mask, masks=None):
+        a = self.attention_layer
+        if not self.training and (a.windowing or a.forward_attn_mask):
+            raise NotImplementedError("layers.Decoder implements neither attn_win nor forward_attn_mask in eval(); "
+                                      "synthesis is the package's Tacotron2.inference")
+        if inputs.dim() != 3 or inputs.shape[2] != self.encoder_embedding_dim:
+            raise ValueError(f"expected inputs [B, L, {self.encoder_embedding_dim}], got {tuple(inputs.shape)}")
+        if memories.dim() != 3 or memories.shape[0] != inputs.shape[0] or memories.shape[2] != self.mel_channels \
+                or memories.shape[1] % self.r or memories.shape[1] < self.r:
+            raise ValueError(f"expected memories [B, T * {self.r}, {self.mel_channels}], got {tuple(memories.shape)}")
+        if not inputs.is_cuda:
+            _native.lib()  # the "no GPU" error where there is none
+            raise RuntimeError("layers.Decoder: the inputs must be CUDA tensors (there is no CPU path)")
+        if inputs.dtype != torch.float32 or memories.dtype != torch.float32:
+            raise ValueError("layers.Decoder: inputs and memories must be float32")
+        B, L, _ = inputs.shape
+        T = memories.shape[1] // self.r
+        if mask is not None:
+            if tuple(mask.shape) != (B, L):
+                raise ValueError(f"expected a mask of shape {(B, L)}, got {tuple(mask.shape)}")
+            mask = (mask != 0).to(inputs.device, torch.uint8).contiguous()
+        if self.training:
+            if masks is None:
+                masks = self._draw_masks(B, T, inputs.device)
+            else:
+                R, MR = self.attention_rnn_dim, self.mel_channels * self.r
+                shapes = dict(prenet=(2, T, B, self.prenet_dim), att=(2, T, B, R), dec=(2, T, B, R), stop=(T, B, R + MR))
+                fixed = {}
+                for k in _MASK_GROUPS:
+                    if k == "prenet" and not self.prenet.prenet_dropout and masks.get(k) is None:
+                        fixed[k] = torch.ones(shapes[k], dtype=torch.uint8, device=inputs.device)
+                        continue
+                    t = masks[k]
+                    if tuple(t.shape) != shapes[k] or t.dtype not in (torch.uint8, torch.bool):
+                        raise ValueError(f"expected a uint8 or bool mask group {k!r} of shape {shapes[k]}, got "
+                                         f"{t.dtype} {tuple(t.shape)}")
+                    fixed[k] = t.to(inputs.device, torch.uint8).contiguous()
+                masks = fixed
+        else:
+            masks = None
+        self.last_masks = masks
+        params = self._params()
+        track = self.training and torch.is_grad_enabled() and (
+            inputs.requires_grad or memories.requires_grad or any(p.requires_grad for p in params))
+        if not track:
+            out, stop, align, _ = self._run_forward(inputs, memories, mask, masks, False)
+        else:
+            out, stop, align, reserve = _DecoderFunction.apply(inputs, memories, self, mask, masks, *params)
+            if self.separate_stopnet:
+                stop = _StopFunction.apply(stop, self, mask, masks, reserve, (B, L, T), *params)
+        return out.view(B, T * self.r, self.mel_channels).transpose(1, 2), stop, align
+
+
+def _is_reference_decoder(dec):
+    need = ("prenet", "attention_rnn", "attention_layer", "decoder_rnn", "linear_projection", "stopnet",
+            "attention_rnn_init", "go_frame_init", "decoder_rnn_inits")
+    return all(hasattr(dec, n) for n in need) and isinstance(getattr(dec, "attention_rnn"), nn.LSTMCell) \
+        and isinstance(getattr(dec, "decoder_rnn"), nn.LSTMCell) and hasattr(dec.prenet, "layers") \
+        and hasattr(dec.attention_layer, "query_layer")
+
+
+def use_device_decoder(model):
+    """Swap ``model.decoder`` (the reference's ``Decoder``, layers/tacotron2.py:97-247, recognised by its structure
+    and attributes) for a ``layers.Decoder`` that carries the same weights on the same device in the same training
+    mode; returns the model.  Raises ``NotImplementedError`` naming the option, before the model is touched, for
+    ``location_attn``, ``trans_agent`` and ``prenet_type="bn"``.  Calling it again changes nothing.  Build the optimizer
+    afterwards: the parameters are new tensors (``model.decoder.stopnet`` is the module ``optimizer_st`` walks).
+    Measured against the same decoder in torch ops on an MI355X: profiles/decoder_train.json ("timing")."""
+    old = model.decoder
+    if isinstance(old, Decoder):
+        return model
+    if not _is_reference_decoder(old):
+        raise TypeError("use_device_decoder: model.decoder is not the reference's Decoder")
+    a, pre = old.attention_layer, old.prenet
+    location = bool(getattr(a, "location_attention", False)) or hasattr(a, "location_layer")
+    trans = bool(getattr(a, "trans_agent", False)) or hasattr(a, "ta")
+    ptype = getattr(pre, "prenet_type", "original")
+    _decoder_unsupported(ptype, trans, location)
+    rnn = old.attention_rnn.hidden_size
+    new = Decoder(old.encoder_embedding_dim, old.mel_channels, old.r, getattr(a, "windowing", False), a.norm, ptype,
+                  getattr(pre, "prenet_dropout", True), a.forward_attn, trans, getattr(a, "forward_attn_mask", False),
+                  location, old.separate_stopnet, prenet_dim=pre.layers[-1].linear_layer.out_features, rnn_dim=rnn,
+                  attention_dim=a.query_layer.linear_layer.out_features)
+    new.load_state_dict(old.state_dict())
+    new.p_attention_dropout = getattr(old, "p_attention_dropout", 0.1)
+    new.p_decoder_dropout = getattr(old, "p_decoder_dropout", 0.1)
+    new.stopnet[0].p = old.stopnet[0].p
+    new.to(next(old.parameters()).device)
+    new.train(old.training)
+    model.decoder = new
+    return model

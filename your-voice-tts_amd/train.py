@@ -9,7 +9,12 @@ is the package's, ``weight_decay(); check_update(); optimizer.step()`` otherwise
 it for ``layers.LSTM`` (``tts_lstm_forward`` / ``tts_lstm_backward``; build the optimizer after the swap); the
 criteria's backward is ``tts_loss_backward``.  ``layers.use_device_convs(model)`` does the same for every conv-BN
 block of ``encoder.convolutions`` and ``postnet.convolutions`` (``layers.ConvBNBlock``: ``tts_convbn_forward`` /
-``tts_convbn_backward``), after which the whole encoder and the whole Postnet train on the device.
+``tts_convbn_backward``), after which the whole encoder and the whole Postnet train on the device, and
+``layers.use_device_decoder(model)`` for the decoder (``layers.Decoder``: ``tts_dectrain_forward`` /
+``tts_dectrain_backward``); with the three swaps every trainable layer of the shipped Tacotron2 configuration runs in
+HIP, and only the embedding lookup and the tensor glue stay torch.  With a separate stopnet the stop tokens of
+``layers.Decoder`` are an autograd node of their own that reads the forward's reserve alone, so the second
+``stop_loss.backward()`` works after the first backward and the main optimizer's step.
 
 Not part of it: the epoch loop, the logging, checkpoints, ``reduce_tensor`` across ranks and the diagnostic
 audio of train.py:171-260.
