@@ -482,7 +482,11 @@ tts_status tts_tacotron_encode_last_path(tts_tacotron* t, int* kinds, int n);
  *   enc [dev] fp32 [B][Lmax][256]; lens [host] int32 [B] (>= 1)
  *   mel [dev] fp32 [B][steps_cap*r][80]; stop [dev] fp32 [B][steps_cap] (sigmoid stop token);
  *   align [dev] fp32 [B][steps_cap][Lmax] or NULL; n_steps [host] int32 [B] out.
- * steps_cap >= max_steps + 1 (the reference stops once t > max_decoder_steps). */
+ * steps_cap >= max_steps + 1 (the reference stops once t > max_decoder_steps).
+ * Padding contract of enc: rows enc[b][j], j >= lens[b], are never read into a result and may hold
+ * anything (NaN included) on both serving paths: every use of them and of their input projection is
+ * selected by j < lens[b], never multiplied by a zero weight.  Lmax may exceed the longest lens[b];
+ * alignment columns j >= lens[b] are written as zero. */
 tts_status tts_tacotron_decode(tts_tacotron* t, const float* enc, const int32_t* lens, int B, int Lmax,
                                int max_steps, int steps_cap, float* mel, float* stop, float* align,
                                int32_t* n_steps, void* stream);

@@ -291,7 +291,8 @@ __global__ __launch_bounds__(TR_THREADS, 1) void tacotron_resident_kernel(const 
             Es[i] = j < La ? a.enc[((int64_t)ba * a.Lcap + j) * TD + d] : 0.f;
         }
         if (tid < TR_PPC) al[tid] = j0 + tid < a.Lcap ? a.alpha[(int64_t)ba * a.Lcap + j0 + tid] : 0.f;
-        if (tid == TR_PPC) al[TR_PPC] = j0 > 0 ? a.alpha[(int64_t)ba * a.Lcap + j0 - 1] : 0.f;
+        // (a handle with Lcap below the slice's start: that slice is empty, its boundary alpha unused)
+        if (tid == TR_PPC) al[TR_PPC] = j0 > 0 && j0 - 1 < a.Lcap ? a.alpha[(int64_t)ba * a.Lcap + j0 - 1] : 0.f;
     }
     if (tid < ADIM) sm[L_V + tid] = a.v[tid];
     const float vb = a.v_b[0];
