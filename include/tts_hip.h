@@ -907,6 +907,79 @@ tts_status tts_dectrain_backward(tts_dectrain* h, const uint8_t* mask, int B, in
                                  const float* reserve, const float* grad_out, const float* grad_stop, float* grad_inputs,
                                  float* grad_memories, const tts_dectrain_grads* g, void* stream);
 
+/* ---------------------------------------------------------------- trainable GRU (gru_train.hip)
+ * The single-layer nn.GRU of the Tacotron / TacotronGST family with its whole backward: the CBHG's
+ * nn.GRU(128, 128, 1, batch_first=True, bidirectional=True) of the encoder and the postnet
+ * (layers/tacotron.py:165-170, :204-205; gradient of `outputs`) and the GST reference encoder's
+ * nn.GRU(256, 128, batch_first=True) (layers/gst_layers.py:53-56, :74-78; gradient of h_n only).  One or two
+ * directions, gate rows r, z, n, fp32, biases on, every sentence at full length T (the reference neither packs
+ * nor masks here).  The cell is ATen's:
+ *   xi = W_ih x_t + b_ih,  hh = W_hh h_prev + b_hh,
+ *   r = s(xi_r + hh_r), z = s(xi_z + hh_z), n = tanh(xi_n + r * hh_n), h = (1 - z) * n + z * h_prev.
+ * All arithmetic is fp32; every matrix product is an exact fp32 MFMA chain (v_mfma_f32_16x16x4_f32) in a fixed
+ * k order (within a 16-k chunk k = 4g + j, the four g inside one MFMA, j over four MFMAs), every
+ * reduction has a fixed order and nothing is accumulated with atomics: the same operands give the same bits,
+ * forward and backward.  The recurrence of a forward is ONE launch, and so is that of a backward: a workgroup
+ * per direction and 16 sentences walks all T steps with its rows of W_hh (W_hh^T) stationary in registers and
+ * the previous state (the previous dpre_h) in LDS; no workgroup waits for another.  The launch count of a call
+ * does not depend on T.  The handle owns the repacked weights and the workspaces (the input projection, dpre_i,
+ * dpre_h, the weight-gradient partials), grown on demand; all calls on one handle must be ordered on one
+ * stream.  The reserve belongs to the caller, so several forwards may be outstanding before their backwards.
+ * No call waits for the stream or copies to or from the host; a workspace that has to grow is freed and
+ * allocated again, which waits for the device that once.  Every [dev] tensor must be 16-byte aligned.
+ * Diagnostic switch: with TTS_GRU_STEPWISE=1 in the environment when the handle is created, its calls launch the
+ * two recurrence kernels once per time step (the state travels through out, dpre_h and a carry buffer; the same
+ * bits).  It exists for the single-launch against per-step-launch comparison of tools/bench_gru_train.py. */
+typedef struct tts_gru tts_gru;
+
+/* UNSUPPORTED unless input_size is a positive multiple of 16 and hidden_size a positive multiple of 16 that
+ * is <= 128 (a direction's W_hh has to fit one workgroup's registers). */
+tts_status tts_gru_create(int input_size, int hidden_size, int bidirectional, tts_gru** out);
+void tts_gru_destroy(tts_gru* g);
+
+/* The parameters of direction d (0: weight_ih_l0 ..., 1: the _reverse set; [1] is not read without the second
+ * direction), [dev] in nn.GRU's layout: w_ih [3H][I], w_hh [3H][H], b_ih, b_hh [3H].  Repacks them on the
+ * stream; call it again whenever the parameters have changed. */
+tts_status tts_gru_set_weights(tts_gru* g, const float* const* w_ih, const float* const* w_hh,
+                               const float* const* b_ih, const float* const* b_hh, void* stream);
+
+/* Floats of the reserve a forward of this shape fills: r, z, n and hh_n = W_hh_n h_prev + b_hh_n of every
+ * position and direction, [B][T][D][4][H].  0 for a null handle or a B or T <= 0. */
+int64_t tts_gru_reserve_floats(const tts_gru* g, int B, int T);
+
+/* `outputs, h_n = gru(x)` (layers/tacotron.py:204-205, layers/gst_layers.py:76-77).
+ *   x        [dev]  [B][T][I]
+ *   h0       [dev]  [D][B][H] or NULL (zeros); a constant: no gradient is produced for it
+ *   out      [dev]  [B][T][D * H] = [h_fwd(t) | h_bwd(t)]
+ *   h_n      [dev]  [D][B][H] or NULL: the forward direction's state after t = T - 1, the reverse one's after 0
+ *   reserve  [dev]  tts_gru_reserve_floats(g, B, T) floats, or NULL (no backward will follow: nothing extra
+ *                   is stored, and out, h_n are bitwise the same)
+ * INVALID before any launch: a null handle, x or out; weights not set; B or T <= 0; B * T >= 2^24; a
+ * misaligned tensor.  2 launches: the input projection of both directions, the recurrence. */
+tts_status tts_gru_forward(tts_gru* g, const float* x, int B, int T, const float* h0, float* out, float* h_n,
+                           float* reserve, void* stream);
+
+/* The backward of that forward.  dh_t = grad_out[:, t] + carry; the carry starts as grad_h_n:
+ *   da_n = dh * (1 - z) * (1 - n^2),  da_z = dh * (h_prev - n) * z * (1 - z),  da_r = da_n * hh_n * r * (1 - r)
+ *   dpre_i = [da_r | da_z | da_n]      grad_W_ih = dpre_i^T x,      grad_b_ih = sum dpre_i,  grad_x = dpre_i W_ih
+ *   dpre_h = [da_r | da_z | da_n * r]  grad_W_hh = dpre_h^T h_prev, grad_b_hh = sum dpre_h
+ *   carry  = dh * z + dpre_h W_hh
+ *   x, B, T, h0   as the forward had them; reserve, out: what it wrote
+ *   grad_out  [dev]  [B][T][D * H] or NULL;  grad_h_n [dev] [D][B][H] or NULL.  A NULL one is read as zero (it is
+ *             not loaded at all); the result is bitwise that of the same call with zeros passed.
+ *   grad_x    [dev]  [B][T][I] out, summed over the directions
+ *   grad_w_ih, grad_w_hh, grad_b_ih, grad_b_hh  [2] of [dev] out in the parameters' layouts ([1] is not read
+ *             without the second direction)
+ * Gradients are WRITTEN, not accumulated.  grad_x, any of the four arrays and any entry of one may be NULL;
+ * that product is skipped.  The weights are those of the last tts_gru_set_weights: they must be the forward's.
+ * INVALID before any launch: as the forward; a null reserve or out; grad_out and grad_h_n both NULL.  One
+ * launch for the recurrence, then at most 11 (column sums, the weight-gradient partials in row chunks of 512
+ * folded in chunk order, grad_x). */
+tts_status tts_gru_backward(tts_gru* g, const float* x, int B, int T, const float* reserve, const float* out,
+                            const float* h0, const float* grad_out, const float* grad_h_n, float* grad_x,
+                            float* const* grad_w_ih, float* const* grad_w_hh, float* const* grad_b_ih,
+                            float* const* grad_b_hh, void* stream);
+
 const char* tts_last_error(void);
 const char* tts_version(void);
 

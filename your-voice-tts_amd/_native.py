@@ -49,6 +49,8 @@ EXPORTS = (
     "tts_optim_decay", "tts_optim_adam", "tts_optim_step",
     "tts_lstm_create", "tts_lstm_destroy", "tts_lstm_set_weights", "tts_lstm_reserve_floats", "tts_lstm_forward",
     "tts_lstm_backward",
+    "tts_gru_create", "tts_gru_destroy", "tts_gru_set_weights", "tts_gru_reserve_floats", "tts_gru_forward",
+    "tts_gru_backward",
     "tts_convbn_create", "tts_convbn_destroy", "tts_convbn_set_weights", "tts_convbn_reserve_floats",
     "tts_convbn_forward", "tts_convbn_backward",
     "tts_dectrain_create", "tts_dectrain_destroy", "tts_dectrain_set_weights", "tts_dectrain_reserve_floats",
@@ -226,6 +228,14 @@ def _declare(lib):
     lib.tts_lstm_reserve_floats.restype = ctypes.c_int64
     lib.tts_lstm_forward.argtypes = [vp, vp, I32P, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp]
     lib.tts_lstm_backward.argtypes = [vp, vp, I32P, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, PP, PP, PP, PP, vp]
+    lib.tts_gru_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
+    lib.tts_gru_destroy.argtypes = [vp]
+    lib.tts_gru_destroy.restype = None
+    lib.tts_gru_set_weights.argtypes = [vp, PP, PP, PP, PP, vp]
+    lib.tts_gru_reserve_floats.argtypes = [vp, ctypes.c_int, ctypes.c_int]
+    lib.tts_gru_reserve_floats.restype = ctypes.c_int64
+    lib.tts_gru_forward.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]
+    lib.tts_gru_backward.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp, PP, PP, PP, PP, vp]
     lib.tts_convbn_create.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(vp)]
     lib.tts_convbn_destroy.argtypes = [vp]
     lib.tts_convbn_destroy.restype = None

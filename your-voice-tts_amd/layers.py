@@ -23,6 +23,11 @@ Without a GPU a call raises the package's "no GPU" RuntimeError; there is no CPU
 ``ConvBNBlock`` is the reference's conv-BN block (layers/tacotron2.py:9-27) with the same ``net`` Sequential, hence
 the same state dict, and ``tts_convbn_forward`` / ``tts_convbn_backward`` (csrc/convbn_train.hip) as its forward and
 backward; ``use_device_convs(model)`` swaps it into ``encoder.convolutions`` and ``postnet.convolutions``.
+
+``GRU`` is the single-layer ``nn.GRU`` of the Tacotron / TacotronGST family (the CBHG's bidirectional one,
+layers/tacotron.py:165-170, and the GST reference encoder's, layers/gst_layers.py:53-56) with ``tts_gru_forward`` /
+``tts_gru_backward`` (csrc/gru_train.hip) as its forward and backward, ``out`` and ``h_n`` both differentiable;
+``use_device_gru(model)`` swaps it in wherever the model has one it implements.
 """
 from __future__ import annotations
 
@@ -825,4 +830,228 @@ def use_device_decoder(model):
     new.to(next(old.parameters()).device)
     new.train(old.training)
     model.decoder = new
+    return model
+
+
+# ---------------------------------------------------------------------- the GRU of the Tacotron / GST family
+_GRU_SUFFIXES = ("", "_reverse")
+
+
+class _GRUFunction(torch.autograd.Function):
+    """forward(x [B, T, I], module, h0, *parameters) -> (out, h_n), both differentiable.  The parameters ride along
+    so that autograd asks for their gradients; the kernels read the module's repacked copies."""
+
+    @staticmethod
+    def forward(ctx, x, module, h0, *params):
+        out, h_n, reserve = module._run_forward(x, h0, True)
+        ctx.save_for_backward(x, out, reserve, *([] if h0 is None else [h0]))
+        ctx.module, ctx.has_h0 = module, h0 is not None
+        ctx.versions = module._key()
+        ctx.set_materialize_grads(False)  # an unused output's gradient stays None: it is not loaded at all
+        return out, h_n
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out, grad_h_n):
+        x, out, reserve, *h0 = ctx.saved_tensors
+        m = ctx.module
+        if m._key() != ctx.versions:
+            raise RuntimeError("layers.GRU: the parameters were modified between this forward and its backward")
+        need = ctx.needs_input_grad
+        if grad_out is None and grad_h_n is None:
+            return (None,) * len(need)
+        grads = m._run_backward(x, reserve, out, h0[0] if ctx.has_h0 else None, grad_out, grad_h_n, need[0], need[3:])
+        return (grads[0], None, None) + tuple(grads[1:])
+
+
+class GRU(nn.Module):
+    """``nn.GRU(input_size, hidden_size, num_layers=1, bias=True, batch_first=True, bidirectional=...)`` on the
+    device, a drop-in for the three GRUs of the reference's Tacotron / TacotronGST: the CBHG's
+    ``nn.GRU(128, 128, 1, batch_first=True, bidirectional=True)`` of the encoder and of the postnet
+    (layers/tacotron.py:165-170, :204-205: ``outputs, _ = gru(x)``) and the GST reference encoder's
+    ``nn.GRU(256, 128, batch_first=True)`` (layers/gst_layers.py:53-56, :74-78: ``_, out = gru(x)``, so only ``h_n`` is
+    differentiated).  ``tts_gru_forward`` / ``tts_gru_backward`` (csrc/gru_train.hip) run the whole time loop of a
+    forward, and of a backward, in one launch each.
+
+    Parameter names, shapes and initialisation are ``nn.GRU``'s, so state dicts load both ways.  ``forward(input,
+    hx=None)`` takes a padded ``[B, T, I]`` tensor, every sentence at full length, and returns ``(out, h_n)``; both
+    join autograd.  ``hx`` is a constant: an ``hx`` that requires grad raises.  A ``PackedSequence`` raises
+    ``NotImplementedError`` (the reference never packs here).  All arithmetic is fp32 on fixed summation orders: the
+    same operands give the same bits, forward and backward.
+
+    With grad mode off, in ``eval()`` mode, or when neither the input nor a parameter requires grad, the forward
+    keeps nothing for a backward (``last_reserve_floats`` is 0) and ``out``, ``h_n`` have the same bits.  The weights
+    are repacked when the parameters' version counters or addresses have changed since the last call (``repacks``
+    counts).  Without a GPU a call raises the package's "no GPU" RuntimeError; there is no CPU fallback."""
+
+    def __init__(self, input_size, hidden_size, num_layers=1, bias=True, batch_first=False, dropout=0.0,
+                 bidirectional=False, device=None, dtype=None):
+        super().__init__()
+        for ok, what in ((num_layers == 1, "num_layers != 1"), (bias, "bias=False"),
+                         (batch_first, "batch_first=False"), (dropout == 0, "dropout"),
+                         (dtype in (None, torch.float32), "a dtype other than float32"),
+                         (input_size > 0 and input_size % 16 == 0, "an input_size that is no multiple of 16"),
+                         (hidden_size > 0 and hidden_size % 16 == 0, "a hidden_size that is no multiple of 16"),
+                         (hidden_size <= 128, "a hidden_size > 128")):
+            if not ok:
+                raise NotImplementedError(f"layers.GRU does not implement {what}")
+        self.input_size, self.hidden_size, self.bidirectional = input_size, hidden_size, bool(bidirectional)
+        self.num_layers, self.bias, self.batch_first, self.dropout = 1, True, True, 0.0
+        G = 3 * hidden_size
+        for suffix in _GRU_SUFFIXES[:self.num_directions]:
+            for name, shape in zip(_NAMES, ((G, input_size), (G, hidden_size), (G,), (G,))):
+                self.register_parameter(name + suffix, nn.Parameter(torch.empty(shape, device=device)))
+        self.reset_parameters()
+        self._h = None
+        self._packed_key = None
+        self.repacks = 0
+        self.last_reserve_floats = 0
+
+    @property
+    def num_directions(self):
+        return 2 if self.bidirectional else 1
+
+    def reset_parameters(self):  # nn.GRU's: U(-1 / sqrt(H), 1 / sqrt(H)) on every parameter
+        k = 1.0 / math.sqrt(self.hidden_size)
+        for p in self.parameters():
+            nn.init.uniform_(p, -k, k)
+
+    def flatten_parameters(self):  # nothing to flatten here
+        pass
+
+    def extra_repr(self):
+        return f"{self.input_size}, {self.hidden_size}, batch_first=True, bidirectional={self.bidirectional}"
+
+    def __del__(self):
+        try:
+            if self._h is not None:
+                self._h[0].tts_gru_destroy(self._h[1])
+        except Exception:
+            pass
+
+    # ------------------------------------------------------------------ the handle and its weights
+    def _params(self):
+        return [getattr(self, n + s) for s in _GRU_SUFFIXES[:self.num_directions] for n in _NAMES]
+
+    def _key(self):
+        return tuple((p.data_ptr(), p._version) for p in self._params())
+
+    def _handle(self):
+        lib = _native.lib()  # raises without a GPU / library: no CPU fallback
+        if self._h is None:
+            h = ctypes.c_void_p()
+            _native.check(lib.tts_gru_create(self.input_size, self.hidden_size, int(self.bidirectional),
+                                             ctypes.byref(h)), "tts_gru_create")
+            self._h = (lib, h)
+        return self._h
+
+    def _sync_weights(self):
+        lib, h = self._handle()
+        key = self._key()
+        if key == self._packed_key:
+            return
+        ps = self._params()
+        for p in ps:
+            if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous() or p.data_ptr() % 16:
+                raise ValueError("layers.GRU: parameters must be contiguous 16-byte aligned CUDA float32 tensors")
+        per = [_ptr_pair([ps[d * 4 + k] for d in range(self.num_directions)] + [None] * (2 - self.num_directions))
+               for k in range(4)]
+        _native.check(lib.tts_gru_set_weights(h, *per, _native.stream_handle()), "tts_gru_set_weights")
+        self._packed_key = key
+        self.repacks += 1
+
+    # ------------------------------------------------------------------ the two calls
+    def _run_forward(self, x, h0, want_reserve):
+        lib, h = self._handle()
+        self._sync_weights()
+        B, T, _ = x.shape
+        D, H = self.num_directions, self.hidden_size
+        x = _aligned(x.detach())
+        out = torch.empty(B, T, D * H, dtype=torch.float32, device=x.device)
+        h_n = torch.empty(D, B, H, dtype=torch.float32, device=x.device)
+        reserve = None
+        if want_reserve:
+            reserve = torch.empty(lib.tts_gru_reserve_floats(h, B, T), dtype=torch.float32, device=x.device)
+        self.last_reserve_floats = 0 if reserve is None else reserve.numel()
+        _native.check(lib.tts_gru_forward(h, _ptr(x), B, T, _ptr(h0), _ptr(out), _ptr(h_n), _ptr(reserve),
+                                          _native.stream_handle()), "tts_gru_forward")
+        return out, h_n, reserve
+
+    def _run_backward(self, x, reserve, out, h0, grad_out, grad_h_n, need_x, need_params):
+        lib, h = self._handle()
+        B, T, _ = x.shape
+        D = self.num_directions
+        x = _aligned(x.detach())
+        grad_out = None if grad_out is None else _aligned(grad_out)
+        grad_h_n = None if grad_h_n is None else _aligned(grad_h_n)
+        grad_x = torch.empty_like(x) if need_x else None
+        ps = self._params()
+        gp = [torch.empty_like(p) if need else None for p, need in zip(ps, need_params)]
+        per = [_ptr_pair([gp[d * 4 + k] for d in range(D)] + [None] * (2 - D)) for k in range(4)]
+        _native.check(lib.tts_gru_backward(h, _ptr(x), B, T, _ptr(reserve), _ptr(out), _ptr(h0), _ptr(grad_out),
+                                           _ptr(grad_h_n), _ptr(grad_x), *per, _native.stream_handle()),
+                      "tts_gru_backward")
+        return [grad_x] + gp
+
+    def forward(self, input, hx=None):
+        if isinstance(input, PackedSequence):
+            raise NotImplementedError("layers.GRU does not implement a PackedSequence input (the reference never "
+                                      "packs here)")
+        x = input
+        if x.dim() != 3 or x.shape[2] != self.input_size:
+            raise ValueError(f"expected input [B, T, {self.input_size}], got {tuple(x.shape)}")
+        if not x.is_cuda:
+            _native.lib()  # the "no GPU" error where there is none
+            raise RuntimeError("layers.GRU: the input must be a CUDA tensor (there is no CPU path)")
+        if x.dtype != torch.float32:
+            raise ValueError(f"layers.GRU: the input must be float32, got {x.dtype}")
+        B, T, _ = x.shape
+        if B < 1 or T < 1:
+            raise ValueError(f"layers.GRU: an empty batch or sequence, input {tuple(x.shape)}")
+        h0 = None
+        if hx is not None:
+            if hx.requires_grad:
+                raise NotImplementedError("layers.GRU: hx is a constant; gradients with respect to it are not "
+                                          "implemented")
+            shape = (self.num_directions, B, self.hidden_size)
+            if tuple(hx.shape) != shape:
+                raise ValueError(f"expected hx {shape}, got {tuple(hx.shape)}")
+            h0 = _aligned(hx.detach().to(x.device, torch.float32))
+        params = self._params()
+        if not (self.training and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))):
+            return self._run_forward(x, h0, False)[:2]
+        return _GRUFunction.apply(x, self, h0, *params)
+
+
+def _gru_implemented(m):
+    return (type(m) is nn.GRU and m.num_layers == 1 and m.bias and m.batch_first and m.dropout == 0
+            and getattr(m, "proj_size", 0) == 0 and m.input_size % 16 == 0 and m.hidden_size % 16 == 0
+            and m.hidden_size <= 128 and m.weight_ih_l0.dtype == torch.float32)
+
+
+def use_device_gru(model):
+    """Swap every ``nn.GRU`` under ``model`` that ``layers.GRU`` implements (one layer, biases, ``batch_first``, no
+    dropout, float32, sizes multiples of 16, ``hidden_size <= 128``) for a ``layers.GRU`` with the same weights on the
+    same device in the same training mode; returns the model.  In the reference's ``Tacotron`` / ``TacotronGST`` those
+    are exactly ``encoder.cbhg.cbhg.gru``, ``postnet.cbhg.gru`` (layers/tacotron.py:165-170) and
+    ``gst.encoder.recurrence`` (layers/gst_layers.py:53-56).  Any other ``nn.GRU`` is left alone; each parameter keeps
+    its ``requires_grad``; a ``model`` that is itself such an ``nn.GRU`` comes back as the ``layers.GRU``.  Calling it
+    again changes nothing.  Build the optimizer afterwards: the parameters are new tensors."""
+    for path, old in list(model.named_modules()):
+        if not _gru_implemented(old):
+            continue
+        new = GRU(old.input_size, old.hidden_size, num_layers=1, bias=True, batch_first=True,
+                  bidirectional=old.bidirectional)
+        new.load_state_dict(old.state_dict())
+        new.to(next(old.parameters()).device)
+        new.train(old.training)
+        for name, p in old.named_parameters():  # a frozen parameter stays frozen
+            getattr(new, name).requires_grad_(p.requires_grad)
+        if not path:  # the model is itself the GRU
+            return new
+        parent = model
+        *head, leaf = path.split(".")
+        for name in head:
+            parent = getattr(parent, name)
+        setattr(parent, leaf, new)
     return model

@@ -14,7 +14,10 @@ block of ``encoder.convolutions`` and ``postnet.convolutions`` (``layers.ConvBNB
 ``tts_dectrain_backward``); with the three swaps every trainable layer of the shipped Tacotron2 configuration runs in
 HIP, and only the embedding lookup and the tensor glue stay torch.  With a separate stopnet the stop tokens of
 ``layers.Decoder`` are an autograd node of their own that reads the forward's reserve alone, so the second
-``stop_loss.backward()`` works after the first backward and the main optimizer's step.
+``stop_loss.backward()`` works after the first backward and the main optimizer's step.  For a Tacotron-family model
+(``c.model in ("Tacotron", "TacotronGST")``) ``layers.use_device_gru(model)`` swaps the three ``nn.GRU``s
+(``encoder.cbhg.cbhg.gru``, ``postnet.cbhg.gru``, ``gst.encoder.recurrence``) for ``layers.GRU`` (``tts_gru_forward`` /
+``tts_gru_backward``; build the optimizer after the swap); the family's other layers stay the caller's torch.
 
 Not part of it: the epoch loop, the logging, checkpoints, ``reduce_tensor`` across ranks and the diagnostic
 audio of train.py:171-260.
